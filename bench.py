@@ -8,9 +8,11 @@
 
 A step = zero grads -> forward (131 MFMA convs + BN/SiLU) -> SimOTA + 24-circle loss -> backward -> (RCCL gradient
 all-reduce) -> fused SGD, on synthetic images / labels already resident in HBM (SURVEY.md 8d generator).
-Rank 0 prints ONE JSON line with the whole-job images/s, the roofline of the dominant kernel (HIP events around
-each of its launches in an instrumented eager step of the same workload) and, at N=1, a CPU baseline: the
-oracle's fp32 train step timed on the host cores on a bounded sample.
+Rank 0 prints ONE JSON line with the whole-job images/s and ms_per_step of the timed steps.  With --full the line also
+carries the roofline of the dominant kernel (HIP events around each of its launches in an instrumented eager step of
+the same workload) and, at N=1, a CPU baseline: the oracle's fp32 train step timed on the host cores on a bounded sample.
+--dump-outputs DIR writes what the last timed step computed (loss vector, head outputs, parameters, gradients, ...)
+as float32 .npy files, so that two builds can be compared output for output on identical seeded inputs.
 """
 import argparse
 import json
@@ -240,6 +242,33 @@ def cpu_baseline(steps=3):
                        "per thread count; best of the sweep" % steps)
 
 
+DUMP_SAMPLE = 3 << 20               # elements: a larger array is written as this fixed, seeded sample of its flat elements
+
+
+def dump_outputs(ts, path):
+    """What the timed path computed in its last step, as float32 .npy files under `path`: the loss vector the step returns,
+    the head outputs of its forward, and the parameters, BatchNorm buffers, gradients (and EMA parameters with --long-run) it
+    left behind.  An array of more than DUMP_SAMPLE elements is written as the elements at np.unique(default_rng(0).integers(
+    0, numel, DUMP_SAMPLE)) of its flat form - the same positions in every run - which keeps the whole set under 64 MB."""
+    import numpy as np
+    arrays = {"loss_result": ts.ws.result, "head_outputs": ts.eng.outputs, "params": ts.home.flat, "grads": ts.home.gflat}
+    if ts.home.bnumel:
+        arrays["bn_buffers"] = ts.home.bflat[:ts.home.bnumel]
+    if ts.ema_home is not None:
+        arrays["ema_params"] = ts.ema_home.flat
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        v = t.detach().float()
+        if v.numel() > DUMP_SAMPLE:
+            idx = np.unique(np.random.default_rng(0).integers(0, v.numel(), DUMP_SAMPLE))
+            v = v.reshape(-1)[torch.from_numpy(idx).to(v.device)]
+        a = v.cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), a)
+        total += a.nbytes
+    assert total <= 64 << 20, total
+
+
 def self_launch(n):
     """Run this script as n ranks under torch.distributed.run (rendezvous on 127.0.0.1, a free port) and relay the output."""
     import socket
@@ -267,6 +296,48 @@ def self_launch(n):
     return rc
 
 
+def roofline(ts, a):
+    """--full: the roofline of the dominant kernel family - HIP events round every conv launch of an instrumented eager pass
+    of the same launch lists, the family's replayed time and HBM traffic from the committed profiles/ records."""
+    fam = instrumented_step(ts)
+    # The dominant kernel family: the conv forward / input-gradient gather-GEMM behind ep24_conv_fwd_bf16 / ep24_conv_dgrad_bf16.
+    # Since round 2 it has two tilings - the halo-patch form (3x3 stride-1 layers with >= 200 tiles of 256 x 128: conv_ring_kernel
+    # since round 4, conv_patch_kernel before and on request) and igemm_dma_kernel (everything else) - over the same 183 launches
+    # that were one kernel in round 1; the line carries the
+    # family and, under "members", each kernel by itself (their average launch durations are what rocprofv3 reports).
+    members = [k for k in ("conv_ring_kernel", "conv_ring_generic_kernel", "conv_patch_kernel", "igemm_dma_kernel", "conv_wreg_kernel") if k in fam]
+    dom = " + ".join(members)
+    f = {key: sum(fam[k][key] for k in members) for key in ("flops", "ms", "launches", "bytes")}
+    ach = f["flops"] / (f["ms"] * 1e-3) / 1e12
+    tr = [(pmc_traffic(REPLAY_PREFIX[k]), fam[k]["launches"]) for k in members]
+    traffic = round(sum(t[0] * n for (t, n) in tr if t[0]) / max(sum(n for (t, n) in tr if t[0]), 1)) if any(t[0] for t, _ in tr) else None
+    traffic_src = tr[0][0][1]
+    # the family's time in the replayed run: a member's launches may run as several device kernels (the six stride-2 input
+    # gradients of igemm_dma_kernel's share are igemm_dma_multi_kernel launches)
+    reps = [replayed_ms_per_step(REPLAY_PREFIX[k]) for k in members]
+    default_cfg = (a.batch, a.size, a.gts, a.backbone, a.width, a.depth) == (20, 640, 10, "darknet", 1.0, 1.0) and not (a.fisheye or a.long_run or a.no_graph or a.plan or a.depthwise)
+    rep_ms = sum(r[0] for r in reps) if (default_cfg and all(r[0] for r in reps)) else None     # the committed profile is of the default workload
+    rep_src = reps[0][1]
+    return {"bound": "mfma", "kernel": dom, "achieved": round(ach, 2), "peak": MFMA_BF16_PEAK_TFLOPS,
+            "unit": "TFLOP/s", "frac": round(ach / MFMA_BF16_PEAK_TFLOPS, 4),
+            "frac_note": "achieved = the family's conv FLOPs over the SUM of its launch durations, HIP events round every launch of an "
+                         "instrumented serial pass of the same launch lists in this run",
+            "frac_replayed": (round(f["flops"] / (rep_ms * 1e-3) / 1e12 / MFMA_BF16_PEAK_TFLOPS, 4) if rep_ms else None),
+            "frac_replayed_note": "the same FLOPs over the family's ms per step in the graph-replayed two-lane run, where kernels of the two "
+                                  "lanes overlap and stretch each other (rocprofv3 --kernel-trace --stats: %s)" % rep_src,
+            "traffic": traffic,
+            "traffic_unit": "bytes per launch (PMC, %s)" % traffic_src,
+            "algorithmic_bytes_per_launch": round(f["bytes"] / f["launches"]),
+            "algorithmic_gflop_per_launch": round(f["flops"] / f["launches"] / 1e9, 3),
+            "launches_per_step": f["launches"], "avg_launch_us": round(f["ms"] * 1e3 / f["launches"], 2),
+            "members": {k: {"achieved": round(fam[k]["flops"] / (fam[k]["ms"] * 1e-3) / 1e12, 2),
+                            "frac": round(fam[k]["flops"] / (fam[k]["ms"] * 1e-3) / 1e12 / MFMA_BF16_PEAK_TFLOPS, 4),
+                            "launches_per_step": fam[k]["launches"], "avg_launch_us": round(fam[k]["ms"] * 1e3 / fam[k]["launches"], 2),
+                            "ms_per_step": round(fam[k]["ms"], 3)} for k in members},
+            "families": {k: {"tflops": round(v["flops"] / (v["ms"] * 1e-3) / 1e12, 2), "ms_per_step": round(v["ms"], 3),
+                             "launches": v["launches"]} for k, v in fam.items()}}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -275,7 +346,11 @@ def main():
     ap.add_argument("--batch", type=int, default=20, help="per-GPU batch (BASELINE config 2: 20)")
     ap.add_argument("--size", type=int, default=640)
     ap.add_argument("--gts", type=int, default=10)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline figure does not need: the roofline of the dominant "
+                    "kernel family (an instrumented eager step, profiles/ records) and, at --gpus 1, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="after the timed steps write what the last one computed to DIR/<name>.npy "
+                    "(float32; arrays above %d elements as a fixed, seeded sample)" % DUMP_SAMPLE)
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--long-run", action="store_true", help="non-default: also run the SURVEY 8f N2 pieces inside the step (L1 "
                     "branch on, ModelEMA fused into the update, a yoloxwarmcos rate pushed every step)")
@@ -291,6 +366,8 @@ def main():
                     "the trainer's default; bf16 (half the xGMI bytes) is the opt-in of train_24p.py --dp-wire bf16")
     ap.add_argument("--bucket-mb", type=int, default=32, help="all-reduce bucket size at --gpus > 1")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # Plain `python bench.py --gpus N`: start the N ranks ourselves (the reference's launcher also spawns its own ranks,
@@ -407,28 +484,12 @@ def main():
         dt = float(tt)
     loss = float(ts.ws.result[0])
     ips = world * a.batch * a.steps / dt
+    if a.dump_outputs and rank == 0:
+        dump_outputs(ts, a.dump_outputs)            # before --full's instrumented pass rewrites the head outputs and gradients
 
     out = None
     if rank == 0:
-        fam = instrumented_step(ts)
-        # The dominant kernel family: the conv forward / input-gradient gather-GEMM behind ep24_conv_fwd_bf16 / ep24_conv_dgrad_bf16.
-        # Since round 2 it has two tilings - the halo-patch form (3x3 stride-1 layers with >= 200 tiles of 256 x 128: conv_ring_kernel
-        # since round 4, conv_patch_kernel before and on request) and igemm_dma_kernel (everything else) - over the same 183 launches
-        # that were one kernel in round 1; the line carries the
-        # family and, under "members", each kernel by itself (their average launch durations are what rocprofv3 reports).
-        members = [k for k in ("conv_ring_kernel", "conv_ring_generic_kernel", "conv_patch_kernel", "igemm_dma_kernel", "conv_wreg_kernel") if k in fam]
-        dom = " + ".join(members)
-        f = {key: sum(fam[k][key] for k in members) for key in ("flops", "ms", "launches", "bytes")}
-        ach = f["flops"] / (f["ms"] * 1e-3) / 1e12
-        tr = [(pmc_traffic(REPLAY_PREFIX[k]), fam[k]["launches"]) for k in members]
-        traffic = round(sum(t[0] * n for (t, n) in tr if t[0]) / max(sum(n for (t, n) in tr if t[0]), 1)) if any(t[0] for t, _ in tr) else None
-        traffic_src = tr[0][0][1]
-        # the family's time in the replayed run: a member's launches may run as several device kernels (the six stride-2 input
-        # gradients of igemm_dma_kernel's share are igemm_dma_multi_kernel launches)
-        reps = [replayed_ms_per_step(REPLAY_PREFIX[k]) for k in members]
-        default_cfg = (a.batch, a.size, a.gts, a.backbone, a.width, a.depth) == (20, 640, 10, "darknet", 1.0, 1.0) and not (a.fisheye or a.long_run or a.no_graph or a.plan or a.depthwise)
-        rep_ms = sum(r[0] for r in reps) if (default_cfg and all(r[0] for r in reps)) else None     # the committed profile is of the default workload
-        rep_src = reps[0][1]
+        roof = roofline(ts, a) if a.full else None
         from ep24 import _lib as _l
         ring_timeouts = int(_l.lib().fn["ep24_conv_ring_timeouts"]())
         if ring_timeouts != 0:
@@ -456,26 +517,10 @@ def main():
                             if dist.is_initialized() else None),
             "step_mfma_frac": round(ips / world * {"darknet": TRAIN_GFLOP_PER_IMAGE, "resnet": 290.7, "densenet": 388.0, "vgg": 1196.0}[a.backbone] * (a.size / 640.0) ** 2 / 1e3
                                     / MFMA_BF16_PEAK_TFLOPS, 4),      # swaps: 3 x 2 x 48.45 / 64.67 GMAC
-            "roofline": {"bound": "mfma", "kernel": dom, "achieved": round(ach, 2), "peak": MFMA_BF16_PEAK_TFLOPS,
-                         "unit": "TFLOP/s", "frac": round(ach / MFMA_BF16_PEAK_TFLOPS, 4),
-                         "frac_note": "achieved = the family's conv FLOPs over the SUM of its launch durations, HIP events round every launch of an "
-                                      "instrumented serial pass of the same launch lists in this run",
-                         "frac_replayed": (round(f["flops"] / (rep_ms * 1e-3) / 1e12 / MFMA_BF16_PEAK_TFLOPS, 4) if rep_ms else None),
-                         "frac_replayed_note": "the same FLOPs over the family's ms per step in the graph-replayed two-lane run, where kernels of the two "
-                                               "lanes overlap and stretch each other (rocprofv3 --kernel-trace --stats: %s)" % rep_src,
-                         "traffic": traffic,
-                         "traffic_unit": "bytes per launch (PMC, %s)" % traffic_src,
-                         "algorithmic_bytes_per_launch": round(f["bytes"] / f["launches"]),
-                         "algorithmic_gflop_per_launch": round(f["flops"] / f["launches"] / 1e9, 3),
-                         "launches_per_step": f["launches"], "avg_launch_us": round(f["ms"] * 1e3 / f["launches"], 2),
-                         "members": {k: {"achieved": round(fam[k]["flops"] / (fam[k]["ms"] * 1e-3) / 1e12, 2),
-                                         "frac": round(fam[k]["flops"] / (fam[k]["ms"] * 1e-3) / 1e12 / MFMA_BF16_PEAK_TFLOPS, 4),
-                                         "launches_per_step": fam[k]["launches"], "avg_launch_us": round(fam[k]["ms"] * 1e3 / fam[k]["launches"], 2),
-                                         "ms_per_step": round(fam[k]["ms"], 3)} for k in members},
-                         "families": {k: {"tflops": round(v["flops"] / (v["ms"] * 1e-3) / 1e12, 2), "ms_per_step": round(v["ms"], 3),
-                                          "launches": v["launches"]} for k, v in fam.items()}},
         }
-        if world == 1 and not a.no_cpu_baseline:
+        if roof is not None:
+            out["roofline"] = roof
+        if a.full and world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
         print(json.dumps(out), flush=True)
     if world > 1:

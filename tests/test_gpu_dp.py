@@ -97,7 +97,7 @@ def test_bench_starts_its_own_ranks(tmp_path):
     env = _env(EP24_REHEARSE=1)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    args = ["--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--batch", "4", "--size", "256", "--width", "0.25", "--depth", "0.33"]
+    args = ["--full", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--batch", "4", "--size", "256", "--width", "0.25", "--depth", "0.33"]
     # fp32 wire (the default, as the reference's DDP and the trainer): bit-equality with one rank
     two = _run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2"] + args, env, timeout=900)
     line2 = [ln for ln in two.splitlines() if ln.startswith("{")]

@@ -12,7 +12,7 @@ WRITE_SIZE need separate passes; their counter CSVs carry the dispatch's start /
 import collections, csv, json, os, shutil, sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PMC_CMD = "rocprofv3 --kernel-trace --pmc %s --output-format csv -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-graph"
+PMC_CMD = "rocprofv3 --kernel-trace --pmc %s --output-format csv -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-graph"
 SQ = "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE"
 
 
@@ -81,7 +81,7 @@ def main():
 
     # ---- rocprofv3 --kernel-trace --stats of the graph-replayed run
     rows = list(csv.DictReader(open(find(os.path.join(pdir, "kt"), "kernel_stats.csv"))))
-    out = ["# rocprofv3 --kernel-trace --stats, `python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline` (%s @ %s)" % (tag, head), "",
+    out = ["# rocprofv3 --kernel-trace --stats, `python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline` (%s @ %s)" % (tag, head), "",
            "%d executions of the step in the process; per-step = total / %d.  Kernels of the two lanes overlap," % (steps, steps),
            "so the per-step column sums to more than the wall time per step.", "",
            "| kernel | calls | avg us | ms per step | % |", "|---|---|---|---|---|"]
@@ -92,7 +92,7 @@ def main():
     open(os.path.join(prof, tag + "_summary.md"), "w").write("\n".join(out) + "\n")
     shutil.copy(find(os.path.join(pdir, "kt"), "kernel_stats.csv"), os.path.join(prof, tag + "_bench_kernel_stats.csv"))
     meta = {"tag": tag, "git_head": head, "steps_in_profiled_process": steps,
-            "command": "rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline",
+            "command": "rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline",
             "kernels": {short(r["Name"]): {"calls": int(r["Calls"]), "avg_us": round(float(r["AverageNs"]) / 1e3, 3),
                                            "ms_per_step": round(float(r["TotalDurationNs"]) / 1e6 / steps, 4)} for r in rows}}
     json.dump(meta, open(os.path.join(prof, tag + "_kernel_meta.json"), "w"), indent=1, sort_keys=True)
