@@ -1,0 +1,578 @@
+// ep24 - evaluation of 24-point detections: COCO-style AP (the evaluateImg + accumulate semantics of pycocotools for one
+// area range "all", no crowd / ignore regions, one maxDets) with matching and accumulation on the GPU.
+//
+//   eval_iou      pairwise IoU matrix [G][D] (double) of GT rows against detections, for tests and for the host API
+//   eval_match    one workgroup per image: GT count / geometry into LDS, the image's detections sorted by (class, score desc,
+//                 p asc) in global scratch, then one wave per class segment greedily matches the first max_dets detections
+//                 against the class's GTs for all 10 IoU thresholds and appends one record per detection
+//   eval_sort     stable LSD radix sort of the records by (class, score desc, image seq, rank)
+//   eval_accumulate  one workgroup per class: cumulative TP / FP counts, precision envelope and the 101 recall look-ups in double
+//
+// Determinism: the only atomics are integer ones whose order does not matter - the GT count per class (a sum) and the
+// append offset of a class segment's records (the sort key fixes the final order; (class, seq, rank) is unique).
+// No floating-point atomics anywhere.
+#include "geom.h"
+
+namespace {
+
+constexpr int EV_T = 10;             // IoU thresholds
+constexpr int EV_R = 101;            // recall thresholds
+constexpr int EV_MAX_L = 256;        // GT rows per image
+constexpr int EV_MAX_DETS = 128;     // detections per (image, class): the rank takes 7 bits of the record key
+constexpr int EV_NONE = 0xFFFF;      // class field of a detection whose class is outside [0, C): sorted last, never recorded
+
+// ascending order of the result = descending order of the score (total order on the fp32 bit patterns)
+__device__ __forceinline__ uint32_t ord_desc(float s) {
+    uint32_t u = __float_as_uint(s);
+    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    return ~u;
+}
+
+// GT geometry from a label row's 50 coordinates (centre, 24 vertices): circle24 = (cx, cy, r[24]) with the expressions of
+// pairwise_kernel (loss.hip); rect = (x0, y0, x1, y1) = min / max over the vertices
+__device__ __forceinline__ void gt_geometry(const float* t50, int iou_type, float* out) {
+    if (iou_type == 0) {
+        out[0] = t50[0];
+        out[1] = t50[1];
+        for (int k = 0; k < 24; ++k) {
+            const float vx = t50[2 + 2 * k] - t50[0], vy = t50[3 + 2 * k] - t50[1];
+            out[2 + k] = sqrtf(vx * vx + vy * vy);
+        }
+    } else {
+        float x0 = INFINITY, y0 = INFINITY, x1 = -INFINITY, y1 = -INFINITY;
+        for (int k = 0; k < 24; ++k) {
+            const float px = t50[2 + 2 * k], py = t50[3 + 2 * k];
+            x0 = fminf(x0, px); x1 = fmaxf(x1, px); y0 = fminf(y0, py); y1 = fmaxf(y1, py);
+        }
+        out[0] = x0; out[1] = y0; out[2] = x1; out[3] = y1;
+    }
+}
+
+// Detection geometry from (cx, cy, r[24]): circle24 keeps it, rect = min / max over c + r_k * (cos, sin)(15 deg * k) with the
+// cos / sin table cs[48] the host computes in float64 and rounds.  NOT post_prepare's NMS rectangle, which keeps the reference's
+// theta * cos(theta) factors (boxes.py:31-33).
+__device__ __forceinline__ void det_geometry(const float* q26, int iou_type, const float* cs, float* out) {
+    if (iou_type == 0) {
+        for (int k = 0; k < 26; ++k) out[k] = q26[k];
+    } else {
+        float x0 = INFINITY, y0 = INFINITY, x1 = -INFINITY, y1 = -INFINITY;
+        for (int k = 0; k < 24; ++k) {
+            const float px = q26[0] + q26[2 + k] * cs[k];
+            const float py = q26[1] + q26[2 + k] * cs[24 + k];
+            x0 = fminf(x0, px); x1 = fmaxf(x1, px); y0 = fminf(y0, py); y1 = fmaxf(y1, py);
+        }
+        out[0] = x0; out[1] = y0; out[2] = x1; out[3] = y1;
+    }
+}
+
+// circle24: mean over the rays of inter / union of the two concentric-ray circles (ray_giou's iou term, geom.h), all fp32
+__device__ __forceinline__ float circle24_iou(const float* g, const float* q) {
+    const float ddx = g[0] - q[0], ddy = g[1] - q[1];
+    const float d = sqrtf(ddx * ddx + ddy * ddy);
+    float acc = 0.f;
+    for (int k = 0; k < 24; ++k) {
+        const float r1 = g[2 + k], r2 = q[2 + k];
+        const float inter = ray_inter(r1, r2, d);
+        const float area1 = EP24_PI_F * (r1 * r1), area2 = EP24_PI_F * (r2 * r2);
+        acc += inter / (area1 + area2 - inter + 1e-6f);
+    }
+    return acc / 24.0f;
+}
+
+// rect: pycocotools-style box IoU in float64 (no +1)
+__device__ __forceinline__ double rect_iou(const float* g, const float* q) {
+    const double gx0 = g[0], gy0 = g[1], gx1 = g[2], gy1 = g[3];
+    const double dx0 = q[0], dy0 = q[1], dx1 = q[2], dy1 = q[3];
+    const double w = fmax(0.0, fmin(gx1, dx1) - fmax(gx0, dx0));
+    const double h = fmax(0.0, fmin(gy1, dy1) - fmax(gy0, dy0));
+    const double inter = w * h;
+    const double ag = (gx1 - gx0) * (gy1 - gy0), ad = (dx1 - dx0) * (dy1 - dy0);
+    return inter / (ag + ad - inter);
+}
+
+__device__ __forceinline__ double pair_iou(const float* g, const float* q, int iou_type) {
+    return iou_type == 0 ? (double)circle24_iou(g, q) : rect_iou(g, q);
+}
+
+__global__ __launch_bounds__(256) void eval_iou_kernel(const float* gt50, const float* det26, int G, int D, int iou_type,
+                                                       const float* cs, double* out) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long)G * D) return;
+    const int g = (int)(i / D), d = (int)(i - (long)g * D);
+    float gg[26], qq[26];
+    gt_geometry(gt50 + (long)g * 50, iou_type, gg);
+    det_geometry(det26 + (long)d * 26, iou_type, cs, qq);
+    out[i] = pair_iou(gg, qq, iou_type);
+}
+
+// Where detection r of image b lives: row = rows + (row_off[b] + a) * ncols with a = keep[b * keep_stride + r] (the NMS output of
+// post_nms) or a = r (keep == null: a concatenation of postprocess rows).  class_conf / class come from conf / cls[row_off[b] + a]
+// (post_prepare's arrays) or from the row's columns 27 / 28 (conf == null).  score = obj * class_conf in fp32, as post_prepare.
+struct DetSrc {
+    const float* rows;
+    int ncols;
+    const int64_t* row_off;
+    const int32_t* keep;
+    int64_t keep_stride;
+    const float* conf;
+    const int32_t* cls;
+};
+
+__device__ __forceinline__ const float* det_row(const DetSrc& s, int b, int r, float& score, int& c, int C) {
+    const int64_t a = s.row_off[b] + (s.keep ? (int64_t)s.keep[(int64_t)b * s.keep_stride + r] : (int64_t)r);
+    const float* row = s.rows + a * s.ncols;
+    float cf;
+    if (s.conf) {
+        cf = s.conf[a];
+        c = s.cls[a];
+    } else {
+        cf = row[27];
+        const float fc = row[28];
+        c = (fc >= 0.f && fc < (float)C) ? (int)fc : EV_NONE;
+    }
+    if (c < 0 || c >= C) c = EV_NONE;
+    const float sc = row[26] * cf;
+    score = sc == 0.f ? 0.f : sc;                          // -0 ranks with +0 (a tie, as in a comparison sort)
+    return row;
+}
+
+__global__ __launch_bounds__(256) void eval_match_kernel(const float* labels, int L, DetSrc src, const int32_t* count, int C,
+                                                         int iou_type, const float* cs, const double* thr, int max_dets,
+                                                         int64_t seq_base, uint64_t* skey, int P, int64_t* rec_key,
+                                                         int32_t* rec_cls, int32_t* rec_p, int32_t* rec_tp, int32_t* rec_count,
+                                                         int32_t* npig, int32_t* err) {
+    __shared__ float g_geo[EV_MAX_L][26];
+    __shared__ int g_cls[EV_MAX_L];
+    __shared__ double thr_sh[EV_T];
+    __shared__ float cs_sh[48];
+    __shared__ int n_sh;
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const float* lab = labels + (long)b * L * EP24_LABEL_COLS;
+    // GT rows: the first n, n = rows whose 51 values sum to > 0 (losses.py:190, as count_gt in assign.hip)
+    if (tid == 0) n_sh = 0;
+    if (tid < EV_T) thr_sh[tid] = fmin(thr[tid], 1.0 - 1e-10);
+    if (tid < 48) cs_sh[tid] = cs[tid];
+    __syncthreads();
+    for (int r = tid; r < L; r += 256) {
+        float s = 0.f;
+        for (int c = 0; c < EP24_LABEL_COLS; ++c) s += lab[r * EP24_LABEL_COLS + c];
+        if (s > 0.f) atomicAdd(&n_sh, 1);
+    }
+    __syncthreads();
+    const int ng = n_sh;
+    for (int i = tid; i < ng; i += 256) {
+        const float* t = lab + (long)i * EP24_LABEL_COLS;
+        const int c = (t[0] >= 0.f && t[0] < (float)C) ? (int)t[0] : -1;
+        g_cls[i] = c;
+        if (c >= 0) atomicAdd(&npig[c], 1);
+        gt_geometry(t + 1, iou_type, g_geo[i]);
+    }
+    const int nd = count[b];
+    if (nd > P || nd < 0) {                               // host sizes P from the plan; never expected
+        if (tid == 0) atomicOr(err, 1);
+        return;
+    }
+    // the image's detections in (class, score desc, p asc) order: bitonic sort of 64-bit keys in global scratch
+    uint64_t* key = skey + (long)b * P;
+    int P2 = 1;
+    while (P2 < nd) P2 <<= 1;
+    for (int i = tid; i < P2; i += 256) {
+        uint64_t k = ~0ull;
+        if (i < nd) {
+            float s;
+            int c;
+            det_row(src, b, i, s, c, C);
+            k = ((uint64_t)c << 48) | ((uint64_t)ord_desc(s) << 16) | (uint64_t)i;
+        }
+        key[i] = k;
+    }
+    __syncthreads();
+    for (int k = 2; k <= P2; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int i = tid; i < P2; i += 256) {
+                const int l = i ^ j;
+                if (l > i) {
+                    const uint64_t ki = key[i], kl = key[l];
+                    const bool up = (i & k) == 0;
+                    if ((ki > kl) == up) { key[i] = kl; key[l] = ki; }
+                }
+            }
+            __syncthreads();
+        }
+    // one wave per class segment (segments dealt round-robin in sorted order)
+    const int64_t seq = seq_base + b;
+    int hcount = 0;
+    for (int base = 0; base < nd; base += 64) {
+        const int j = base + lane;
+        const uint64_t kj = j < nd ? key[j] : ~0ull;
+        const int cj = (int)(kj >> 48);
+        const int cp = (j > 0 && j < nd) ? (int)(key[j - 1] >> 48) : -1;
+        unsigned long long hm = __ballot(j < nd && cj != cp && cj != EV_NONE);
+        while (hm) {
+            const int hl = __ffsll((long long)hm) - 1;
+            hm &= hm - 1;
+            if ((hcount++ & 3) != w) continue;
+            const int s0 = base + hl;
+            const int c = __shfl(cj, hl, 64);
+            // kept detections: the first min(len, max_dets) of the segment
+            int m = 0;
+            for (int q = 0; q < max_dets; q += 64) {
+                const int jj = s0 + q + lane;
+                const bool in = q + lane < max_dets && jj < nd && (int)(key[jj] >> 48) == c;
+                m += __popcll(__ballot(in));
+            }
+            // this lane's GTs of class c: rows lane, lane + 64, lane + 128, lane + 192
+            bool has[4];
+            bool any = false;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int gi = q * 64 + lane;
+                has[q] = gi < ng && g_cls[gi] == c;
+                any |= has[q];
+            }
+            any = __ballot(any) != 0;
+            int rbase = 0;
+            if (lane == 0) rbase = atomicAdd(rec_count, m);
+            rbase = __shfl(rbase, 0, 64);
+            unsigned matched[4] = {0u, 0u, 0u, 0u};
+            for (int r = 0; r < m; ++r) {
+                const uint64_t kr = key[s0 + r];
+                const int p = (int)(kr & 0xFFFF);
+                const uint32_t sbits = (uint32_t)(kr >> 16);
+                int tpm = 0;
+                if (any) {
+                    float sc;
+                    int cc;
+                    const float* row = det_row(src, b, p, sc, cc, C);
+                    float qg[26];
+                    det_geometry(row, iou_type, cs_sh, qg);
+                    double iou[4];
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) iou[q] = has[q] ? pair_iou(g_geo[q * 64 + lane], qg, iou_type) : -1.0;
+                    for (int t = 0; t < EV_T; ++t) {
+                        // pycocotools: the largest IoU >= min(t, 1 - 1e-10) among unmatched GTs, equal IoUs -> the later GT row
+                        double best = thr_sh[t];
+                        int bg = -1;
+#pragma unroll
+                        for (int q = 0; q < 4; ++q)
+                            if (has[q] && !((matched[q] >> t) & 1u) && iou[q] >= best) { best = iou[q]; bg = q * 64 + lane; }
+                        if (__ballot(bg >= 0) == 0) continue;
+                        for (int o = 32; o > 0; o >>= 1) {
+                            const double ob = __shfl_xor(best, o, 64);
+                            const int og = __shfl_xor(bg, o, 64);
+                            if (og >= 0 && (bg < 0 || ob > best || (ob == best && og > bg))) { best = ob; bg = og; }
+                        }
+                        tpm |= 1 << t;
+                        if ((bg & 63) == lane) matched[bg >> 6] |= 1u << t;
+                    }
+                }
+                if (lane == 0) {
+                    const int64_t o = (int64_t)rbase + r;
+                    rec_key[o] = (int64_t)(((uint64_t)sbits << 32) | ((uint64_t)seq << 7) | (uint64_t)r);
+                    rec_cls[o] = c;
+                    rec_p[o] = p;
+                    rec_tp[o] = tpm;
+                }
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------- radix sort of the records
+// Stable LSD passes of 8 bits over the 96-bit value (class << 64 | key); tile of EV_TILE records per workgroup.
+constexpr int EV_TILE = 4096;
+
+__device__ __forceinline__ int digit_of(int64_t k, int32_t c, int shift) {
+    return shift < 64 ? (int)(((uint64_t)k >> shift) & 255u) : (int)(((uint32_t)c >> (shift - 64)) & 255u);
+}
+
+__global__ __launch_bounds__(256) void radix_hist_kernel(const int64_t* key, const int32_t* cls, int64_t n, int shift, int nblk,
+                                                         int32_t* hist) {
+    __shared__ int h[256];
+    h[threadIdx.x] = 0;
+    __syncthreads();
+    const int64_t base = (int64_t)blockIdx.x * EV_TILE;
+    for (int r = 0; r < EV_TILE / 256; ++r) {
+        const int64_t i = base + r * 256 + threadIdx.x;
+        if (i < n) atomicAdd(&h[digit_of(key[i], cls[i], shift)], 1);
+    }
+    __syncthreads();
+    hist[(int64_t)threadIdx.x * nblk + blockIdx.x] = h[threadIdx.x];
+}
+
+// exclusive prefix sum of m int32 counts, one workgroup of 1024 (each thread 4 consecutive entries per chunk of 4096)
+__global__ __launch_bounds__(1024) void scan_excl_kernel(int32_t* a, int64_t m) {
+    __shared__ int ws[16];
+    __shared__ int carry_sh;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    if (tid == 0) carry_sh = 0;
+    __syncthreads();
+    for (int64_t base = 0; base < m; base += 4096) {
+        int v[4], s = 0;
+        for (int q = 0; q < 4; ++q) {
+            const int64_t i = base + tid * 4 + q;
+            v[q] = i < m ? a[i] : 0;
+            s += v[q];
+        }
+        int incl = s;
+        for (int o = 1; o < 64; o <<= 1) {
+            const int x = __shfl_up(incl, o, 64);
+            if (lane >= o) incl += x;
+        }
+        if (lane == 63) ws[w] = incl;
+        __syncthreads();
+        int pre = carry_sh;
+        for (int q = 0; q < w; ++q) pre += ws[q];
+        int run = pre + incl - s;
+        for (int q = 0; q < 4; ++q) {
+            const int64_t i = base + tid * 4 + q;
+            if (i < m) a[i] = run;
+            run += v[q];
+        }
+        __syncthreads();
+        if (tid == 0) {
+            int t = 0;
+            for (int q = 0; q < 16; ++q) t += ws[q];
+            carry_sh += t;
+        }
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(256) void radix_scatter_kernel(const int64_t* key, const int32_t* cls, const int32_t* idx, int64_t n,
+                                                            int shift, int nblk, const int32_t* hist, int64_t* key_o, int32_t* cls_o,
+                                                            int32_t* idx_o) {
+    __shared__ int off[256];
+    __shared__ int wc[4][256];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    off[tid] = hist[(int64_t)tid * nblk + blockIdx.x];
+    const int64_t base = (int64_t)blockIdx.x * EV_TILE;
+    const unsigned long long lt = (1ull << lane) - 1ull;
+    for (int r = 0; r < EV_TILE / 256; ++r) {
+        for (int q = 0; q < 4; ++q) wc[q][tid] = 0;
+        __syncthreads();
+        const int64_t i = base + r * 256 + tid;
+        const bool valid = i < n;
+        int64_t k = 0;
+        int32_t c = 0, x = 0;
+        int d = 0;
+        if (valid) {
+            k = key[i];
+            c = cls[i];
+            x = idx ? idx[i] : (int32_t)i;
+            d = digit_of(k, c, shift);
+        }
+        unsigned long long mm = __ballot(valid);
+        for (int bit = 0; bit < 8; ++bit) {
+            const unsigned long long bb = __ballot((d >> bit) & 1);
+            mm &= ((d >> bit) & 1) ? bb : ~bb;
+        }
+        const int rank = __popcll(mm & lt);
+        if (valid && rank == 0) wc[w][d] = __popcll(mm);
+        __syncthreads();
+        if (valid) {
+            int pos = off[d] + rank;
+            for (int q = 0; q < w; ++q) pos += wc[q][d];
+            key_o[pos] = k;
+            cls_o[pos] = c;
+            idx_o[pos] = x;
+        }
+        __syncthreads();
+        off[tid] += wc[0][tid] + wc[1][tid] + wc[2][tid] + wc[3][tid];
+        __syncthreads();
+    }
+}
+
+// ---------------------------------------------------------------------------------------------- accumulation
+__global__ __launch_bounds__(256) void class_range_kernel(const int32_t* order, const int32_t* rec_cls, int64_t n, int C,
+                                                          int64_t* range) {
+    for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < n; j += (int64_t)gridDim.x * 256) {
+        const int c = rec_cls[order[j]];
+        if (j == 0 || rec_cls[order[j - 1]] != c) range[2 * c] = j;
+        if (j == n - 1 || rec_cls[order[j + 1]] != c) range[2 * c + 1] = j + 1;
+    }
+}
+
+// one workgroup per class k: pycocotools accumulate for one area range and one maxDets
+__global__ __launch_bounds__(256) void accumulate_kernel(const int32_t* order, const int32_t* rec_tp, const int64_t* range,
+                                                         const int32_t* npig, int C, const double* rthr, int32_t* ctp, double* env,
+                                                         double* precision, double* recall) {
+    __shared__ int wsi[4];
+    __shared__ double wsd[4];
+    __shared__ int carry_i;
+    __shared__ double carry_d;
+    const int k = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int np = npig[k];
+    if (np == 0) {                                        // no GT of this class: excluded (-1), as pycocotools
+        for (int i = tid; i < EV_T * EV_R; i += 256) precision[(int64_t)i * C + k] = -1.0;
+        if (tid < EV_T) recall[tid * C + k] = -1.0;
+        return;
+    }
+    const int64_t s = range[2 * k], n = range[2 * k + 1] - s;
+    const double dnp = (double)np;
+    for (int t = 0; t < EV_T; ++t) {
+        // tp_j = inclusive count of TPs at threshold t; pr_j = tp / (tp + fp + eps) with tp + fp = j + 1
+        if (tid == 0) carry_i = 0;
+        __syncthreads();
+        for (int64_t b0 = 0; b0 < n; b0 += 1024) {
+            int v[4], sum = 0;
+            for (int q = 0; q < 4; ++q) {
+                const int64_t j = b0 + tid * 4 + q;
+                v[q] = j < n ? (rec_tp[order[s + j]] >> t) & 1 : 0;
+                sum += v[q];
+            }
+            int incl = sum;
+            for (int o = 1; o < 64; o <<= 1) {
+                const int x = __shfl_up(incl, o, 64);
+                if (lane >= o) incl += x;
+            }
+            if (lane == 63) wsi[w] = incl;
+            __syncthreads();
+            int run = carry_i + incl - sum;
+            for (int q = 0; q < w; ++q) run += wsi[q];
+            for (int q = 0; q < 4; ++q) {
+                const int64_t j = b0 + tid * 4 + q;
+                run += v[q];
+                if (j < n) {
+                    ctp[s + j] = run;
+                    env[s + j] = (double)run / ((double)(j + 1) + 2.220446049250313e-16);
+                }
+            }
+            __syncthreads();
+            if (tid == 0) carry_i += wsi[0] + wsi[1] + wsi[2] + wsi[3];
+            __syncthreads();
+        }
+        // envelope: pr_j = max over i >= j (chunks from the right)
+        if (tid == 0) carry_d = 0.0;
+        __syncthreads();
+        const int64_t nch = (n + 1023) / 1024;
+        for (int64_t ch = nch - 1; ch >= 0; --ch) {
+            const int64_t b0 = ch * 1024;
+            double v[4];
+            double mx = 0.0;
+            for (int q = 3; q >= 0; --q) {
+                const int64_t j = b0 + tid * 4 + q;
+                v[q] = j < n ? env[s + j] : 0.0;
+                mx = fmax(mx, v[q]);
+            }
+            double incl = mx;                             // suffix max over this lane and the lanes above it
+            for (int o = 1; o < 64; o <<= 1) {
+                const double x = __shfl_down(incl, o, 64);
+                if (lane + o < 64) incl = fmax(incl, x);
+            }
+            if (lane == 0) wsd[w] = incl;
+            __syncthreads();
+            double run = carry_d;
+            for (int q = w + 1; q < 4; ++q) run = fmax(run, wsd[q]);
+            const double above = __shfl_down(incl, 1, 64);
+            if (lane < 63) run = fmax(run, above);
+            for (int q = 3; q >= 0; --q) {
+                const int64_t j = b0 + tid * 4 + q;
+                run = fmax(run, v[q]);
+                if (j < n) env[s + j] = run;
+            }
+            __syncthreads();
+            if (tid == 0) carry_d = fmax(fmax(fmax(carry_d, wsd[0]), fmax(wsd[1], wsd[2])), wsd[3]);
+            __syncthreads();
+        }
+        // the 101 recall thresholds: precision at the first j with rc_j >= r (searchsorted 'left'), 0 past the end
+        if (tid < EV_R) {
+            const double rt = rthr[tid];
+            int64_t lo = 0, hi = n;
+            while (lo < hi) {
+                const int64_t mid = (lo + hi) >> 1;
+                if ((double)ctp[s + mid] / dnp >= rt) hi = mid; else lo = mid + 1;
+            }
+            precision[((int64_t)t * EV_R + tid) * C + k] = lo < n ? env[s + lo] : 0.0;
+        }
+        if (tid == 0) recall[t * C + k] = n ? (double)ctp[s + n - 1] / dnp : 0.0;
+        __syncthreads();
+    }
+}
+
+}  // namespace
+
+#define S_ (hipStream_t) stream
+
+extern "C" int ep24_eval_iou(const float* gt50, const float* det26, int G, int D, int iou_type, const float* ray_cs, double* out,
+                             void* stream) {
+    if ((long)G * D == 0) return EP24_OK;
+    EP24_REQUIRE(gt50 && det26 && ray_cs && out && G > 0 && D > 0, EP24_E_ARG, "eval_iou: bad arguments");
+    EP24_REQUIRE(iou_type == 0 || iou_type == 1, EP24_E_UNSUPPORTED, "eval_iou: iou_type %d (0 circle24, 1 rect)", iou_type);
+    hipLaunchKernelGGL(eval_iou_kernel, dim3((unsigned)(((long)G * D + 255) / 256)), dim3(256), 0, S_, gt50, det26, G, D, iou_type,
+                       ray_cs, out);
+    EP24_LAUNCH_CHECK("ep24_eval_iou");
+    return EP24_OK;
+}
+
+extern "C" int ep24_eval_match(const float* labels, int L, int B, const float* rows, int ncols, const int64_t* row_off,
+                               const int32_t* keep, int64_t keep_stride, const int32_t* count, const float* conf, const int32_t* cls,
+                               int num_classes, int iou_type, const float* ray_cs, const double* iou_thr, int max_dets,
+                               int64_t seq_base, int64_t* sort_scratch, int P, int64_t* rec_key, int32_t* rec_cls, int32_t* rec_p,
+                               int32_t* rec_tp, int32_t* rec_count, int32_t* npig, int32_t* err, void* stream) {
+    if (B == 0) return EP24_OK;
+    EP24_REQUIRE(labels && rows && row_off && count && ray_cs && iou_thr && sort_scratch && rec_key && rec_cls && rec_p && rec_tp &&
+                 rec_count && npig && err && B > 0 && P > 0, EP24_E_ARG, "eval_match: bad arguments");
+    EP24_REQUIRE((conf == nullptr) == (cls == nullptr), EP24_E_ARG, "eval_match: conf and cls come together");
+    EP24_REQUIRE(ncols >= (conf ? 27 : 29), EP24_E_ARG, "eval_match: ncols=%d", ncols);
+    EP24_REQUIRE(L >= 0 && L <= EV_MAX_L, EP24_E_UNSUPPORTED, "eval_match: %d GT rows per image (at most %d)", L, EV_MAX_L);
+    EP24_REQUIRE(max_dets > 0 && max_dets <= EV_MAX_DETS, EP24_E_UNSUPPORTED, "eval_match: max_dets=%d (1..%d)", max_dets, EV_MAX_DETS);
+    EP24_REQUIRE(num_classes > 0 && num_classes < EV_NONE, EP24_E_UNSUPPORTED, "eval_match: num_classes=%d (1..%d)", num_classes,
+                 EV_NONE - 1);
+    EP24_REQUIRE(P <= 65536 && (P & (P - 1)) == 0, EP24_E_UNSUPPORTED, "eval_match: P=%d (a power of two, at most 65536 detections per image)", P);
+    EP24_REQUIRE(seq_base >= 0 && seq_base + B <= (1LL << 25), EP24_E_UNSUPPORTED, "eval_match: image sequence %lld + %d beyond 2^25",
+                 (long long)seq_base, B);
+    EP24_REQUIRE(iou_type == 0 || iou_type == 1, EP24_E_UNSUPPORTED, "eval_match: iou_type %d (0 circle24, 1 rect)", iou_type);
+    DetSrc src{rows, ncols, row_off, keep, keep_stride, conf, cls};
+    hipLaunchKernelGGL(eval_match_kernel, dim3(B), dim3(256), 0, S_, labels, L, src, count, num_classes, iou_type, ray_cs, iou_thr,
+                       max_dets, seq_base, (uint64_t*)sort_scratch, P, rec_key, rec_cls, rec_p, rec_tp, rec_count, npig, err);
+    EP24_LAUNCH_CHECK("ep24_eval_match");
+    return EP24_OK;
+}
+
+extern "C" int ep24_eval_sort(const int64_t* key, const int32_t* cls, int64_t n, int key_low_bits, int cls_bits, int64_t* key_tmp,
+                              int32_t* cls_tmp, int32_t* idx_tmp, int32_t* hist, int32_t* order, void* stream) {
+    if (n == 0) return EP24_OK;
+    EP24_REQUIRE(key && cls && key_tmp && cls_tmp && idx_tmp && hist && order && n > 0, EP24_E_ARG, "eval_sort: bad arguments");
+    EP24_REQUIRE(n <= 0x7FFFFFFFLL, EP24_E_UNSUPPORTED, "eval_sort: %lld records (at most 2^31 - 1)", (long long)n);
+    EP24_REQUIRE(key_low_bits >= 0 && key_low_bits <= 32 && cls_bits >= 0 && cls_bits <= 32, EP24_E_ARG, "eval_sort: bit counts");
+    const int nblk = (int)((n + EV_TILE - 1) / EV_TILE);
+    int shifts[16], np = 0;
+    for (int sft = 0; sft < key_low_bits; sft += 8) shifts[np++] = sft;
+    for (int sft = 32; sft < 64; sft += 8) shifts[np++] = sft;
+    for (int sft = 0; sft < cls_bits; sft += 8) shifts[np++] = 64 + sft;
+    const int64_t* kin = key;
+    const int32_t* cin = cls;
+    const int32_t* iin = nullptr;
+    for (int p = 0; p < np; ++p) {
+        int64_t* ko = key_tmp + (p & 1) * n;
+        int32_t* co = cls_tmp + (p & 1) * n;
+        int32_t* io = (p == np - 1) ? order : idx_tmp + (p & 1) * n;
+        hipLaunchKernelGGL(radix_hist_kernel, dim3(nblk), dim3(256), 0, S_, kin, cin, n, shifts[p], nblk, hist);
+        hipLaunchKernelGGL(scan_excl_kernel, dim3(1), dim3(1024), 0, S_, hist, (int64_t)256 * nblk);
+        hipLaunchKernelGGL(radix_scatter_kernel, dim3(nblk), dim3(256), 0, S_, kin, cin, iin, n, shifts[p], nblk, hist, ko, co, io);
+        kin = ko;
+        cin = co;
+        iin = io;
+    }
+    EP24_LAUNCH_CHECK("ep24_eval_sort");
+    return EP24_OK;
+}
+
+extern "C" int ep24_eval_accumulate(const int32_t* order, const int32_t* rec_cls, const int32_t* rec_tp, int64_t n, const int32_t* npig,
+                                    int num_classes, const double* rec_thr, int64_t* cls_range, int32_t* ctp_scratch,
+                                    double* env_scratch, double* precision, double* recall, void* stream) {
+    EP24_REQUIRE(npig && rec_thr && cls_range && precision && recall && num_classes > 0, EP24_E_ARG, "eval_accumulate: bad arguments");
+    EP24_REQUIRE(n == 0 || (order && rec_cls && rec_tp && ctp_scratch && env_scratch), EP24_E_ARG, "eval_accumulate: null record buffer");
+    EP24_REQUIRE(hipMemsetAsync(cls_range, 0, sizeof(int64_t) * 2 * (size_t)num_classes, S_) == hipSuccess, EP24_E_LAUNCH,
+                 "eval_accumulate: memset failed");
+    if (n > 0) {
+        const long blocks = (n + 255) / 256;
+        hipLaunchKernelGGL(class_range_kernel, dim3((unsigned)(blocks > 4096 ? 4096 : blocks)), dim3(256), 0, S_, order, rec_cls, n,
+                           num_classes, cls_range);
+    }
+    hipLaunchKernelGGL(accumulate_kernel, dim3(num_classes), dim3(256), 0, S_, order, rec_tp, cls_range, npig, num_classes, rec_thr,
+                       ctp_scratch, env_scratch, precision, recall);
+    EP24_LAUNCH_CHECK("ep24_eval_accumulate");
+    return EP24_OK;
+}

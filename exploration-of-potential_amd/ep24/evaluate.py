@@ -1,0 +1,316 @@
+"""COCO-style AP of 24-point detections on the GPU (csrc/evaluate.hip).
+
+The reference scores axis-aligned boxes through pycocotools and never wires an evaluator into its 24-point trainer
+(exp/yolox_base.py ``get_evaluator`` is commented out).  ``Evaluator24`` gives the trainer a validation metric with the
+semantics of pycocotools ``evaluateImg`` + ``accumulate`` for one area range ("all"), no crowd / ignore regions and one
+``maxDets``, over two IoU types:
+
+* ``"circle24"`` (default): the model's own geometry - per ray the IoU of the GT's and the detection's ray circles
+  (``ray_inter`` of geom.h), averaged over the 24 rays in fp32.  A similarity in [0, 1], not the loss's GIoU.
+* ``"rect"``: the bounding boxes of the 24 points (detections: c + r_k (cos, sin)(15 deg k)), IoU in float64.
+
+Matching (per image and class, all 10 thresholds), the sort of the records over the whole evaluation and the accumulation
+run as HIP kernels; the host reads one count per batch and, in ``summarize``, the [10, 101, C] precision and [10, C] recall
+tables once.  Torch only allocates and copies.
+"""
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import Ep24Error, call, ptr, stream_ptr
+
+IOU_TYPES = {"circle24": 0, "rect": 1}
+IOU_THRS = np.linspace(0.5, 0.95, 10)                    # float64, as pycocotools Params
+REC_THRS = np.linspace(0.0, 1.0, 101)
+MAX_GT_ROWS = 256
+MAX_DETS = 128
+
+
+def ray_cos_sin():
+    """[48] fp32: cos(15 deg * k) then sin(15 deg * k), computed in float64 and rounded."""
+    th = np.arange(24, dtype=np.float64) * (15.0 * np.pi / 180.0)
+    return np.concatenate([np.cos(th), np.sin(th)]).astype(np.float32)
+
+
+def _iou_type(iou_type):
+    if iou_type not in IOU_TYPES:
+        raise ValueError("iou_type must be one of %s, got %r" % (sorted(IOU_TYPES), iou_type))
+    return IOU_TYPES[iou_type]
+
+
+_consts = {}
+
+
+def _device_consts(dev):
+    key = str(dev)
+    c = _consts.get(key)
+    if c is None:
+        c = _consts[key] = (torch.from_numpy(ray_cos_sin()).to(dev), torch.from_numpy(IOU_THRS.copy()).to(dev),
+                            torch.from_numpy(REC_THRS.copy()).to(dev))
+    return c
+
+
+def pairwise_iou(gt50, det26, iou_type="circle24"):
+    """IoU matrix [G, D] float64 of GT rows ``gt50 [G, 50]`` (centre + 24 vertices in pixels: label columns 1..50) against
+    detections ``det26 [D, 26]`` (centre + 24 radii), both on the GPU."""
+    _lib.require_gpu()
+    t = _iou_type(iou_type)
+    if not (gt50.is_cuda and det26.is_cuda):
+        raise Ep24Error("ep24: pairwise_iou takes GPU tensors (no CPU fallback on the product path)")
+    if gt50.dim() != 2 or gt50.shape[1] != 50 or det26.dim() != 2 or det26.shape[1] != 26:
+        raise IndexError("expected gt50 [G, 50] and det26 [D, 26], got %s and %s" % (tuple(gt50.shape), tuple(det26.shape)))
+    g = gt50.detach().float().contiguous()
+    d = det26.detach().float().contiguous()
+    out = torch.empty(g.shape[0], d.shape[0], dtype=torch.float64, device=g.device)
+    cs, _, _ = _device_consts(g.device)
+    call("eval_iou", ptr(g), ptr(d), g.shape[0], d.shape[0], t, ptr(cs), ptr(out), stream_ptr())
+    return out
+
+
+class _MatchScratch:
+    """Per-batch buffers of the match kernel for B images of at most P detections and ``cap`` records."""
+
+    def __init__(self, B, P, cap, dev):
+        f = dict(device=dev)
+        self.sort = torch.empty(B * P, dtype=torch.int64, **f)
+        self.key = torch.empty(cap, dtype=torch.int64, **f)
+        self.cls = torch.empty(cap, dtype=torch.int32, **f)
+        self.p = torch.empty(cap, dtype=torch.int32, **f)
+        self.tp = torch.empty(cap, dtype=torch.int32, **f)
+        self.count = torch.zeros(1, dtype=torch.int32, **f)
+
+
+_match_scratch = {}
+
+
+def _h2d(a, dev):
+    """A small host array on the device without a host synchronisation (page-locked staging, asynchronous copy)."""
+    return torch.from_numpy(np.ascontiguousarray(a)).pin_memory().to(dev, non_blocking=True)
+
+
+_row_offs = {}
+
+
+def _pow2(n):
+    P = 1
+    while P < n:
+        P <<= 1
+    return P
+
+
+class Evaluator24:
+    """``Evaluator24(num_classes, iou_type="circle24", max_dets=100, conf_thre=0.01, nms_thre=0.65)``.
+
+    ``update(predictions, labels)``: decoded eval-mode predictions [B, A, 27 + C] (the evaluator runs post_prepare +
+    post_nms itself) and the label table [B, L, 51]; ``update_detections(dets, labels)``: ``ep24.infer.postprocess`` output.
+    Both give bit-identical results for the same detections.  ``summarize()`` returns a dict with ``AP`` (0.5:0.95),
+    ``AP50``, ``AP75``, ``AR100``, ``per_class_AP`` and the tables; ``summary`` holds the printed form."""
+
+    def __init__(self, num_classes, iou_type="circle24", max_dets=100, conf_thre=0.01, nms_thre=0.65, device=None):
+        if not 0 < int(num_classes) < 0xFFFF:
+            raise Ep24Error("ep24: Evaluator24 takes 1 .. 65534 classes, got %d (EP24_E_UNSUPPORTED)" % num_classes)
+        if not 0 < int(max_dets) <= MAX_DETS:
+            raise Ep24Error("ep24: max_dets=%d: at most %d detections per image and class (EP24_E_UNSUPPORTED)" % (max_dets, MAX_DETS))
+        self.num_classes = int(num_classes)
+        self.iou_type = iou_type
+        self._t = _iou_type(iou_type)
+        self.max_dets = int(max_dets)
+        self.conf_thre, self.nms_thre = float(conf_thre), float(nms_thre)
+        self.device = device
+        self.reset()
+
+    def reset(self):
+        self._recs = []                                   # per batch: (key, cls, p, tp) device tensors
+        self._npig = None
+        self._err = None
+        self.seq = 0                                      # images seen: the next image's sequence number
+        self.n_records = 0
+        self.stats = None
+
+    # ---- inputs ------------------------------------------------------------------------------------
+    def _prepare(self, labels, dev):
+        _lib.require_gpu()
+        if labels.dim() != 3 or labels.shape[2] != 51:
+            raise IndexError("expected labels [B, L, 51], got %s" % (tuple(labels.shape),))
+        if labels.shape[1] > MAX_GT_ROWS:
+            raise Ep24Error("ep24: %d GT rows per image: at most %d (EP24_E_UNSUPPORTED)" % (labels.shape[1], MAX_GT_ROWS))
+        if self._npig is None:
+            self.device = dev
+            self._npig = torch.zeros(self.num_classes, dtype=torch.int32, device=dev)
+            self._err = torch.zeros(1, dtype=torch.int32, device=dev)
+        return labels.detach().to(dev).float().contiguous()
+
+    def update(self, predictions, labels):
+        """predictions [B, A, 27 + C] decoded (sigmoid scores) on the GPU, labels [B, L, 51]."""
+        _lib.require_gpu()
+        if not predictions.is_cuda:
+            raise Ep24Error("ep24: predictions must live on the GPU (no CPU fallback on the product path)")
+        C = self.num_classes
+        if predictions.dim() != 3 or predictions.shape[2] != 27 + C:
+            raise IndexError("expected predictions [B, A, 27 + %d], got %s" % (C, tuple(predictions.shape)))
+        B, A, ncols = predictions.shape
+        if labels.shape[0] != B:
+            raise IndexError("predictions hold %d images, labels %d" % (B, labels.shape[0]))
+        if A > 65536:
+            raise Ep24Error("ep24: %d anchors per image: at most 65536 (EP24_E_UNSUPPORTED)" % A)
+        pred = predictions.detach().float().contiguous()
+        lab = self._prepare(labels, pred.device)
+        if B == 0 or A == 0:
+            self.seq += B
+            return
+        from . import infer
+        key = (B, A, str(pred.device))
+        ws = infer._scratch.get(key)
+        if ws is None:
+            ws = infer._scratch[key] = infer._Scratch(B, A, pred.device)
+        s = stream_ptr()
+        call("post_prepare", ptr(pred), ncols, C, B * A, self.conf_thre, ptr(ws.ray), ptr(ws.score), ptr(ws.conf), ptr(ws.cls),
+             ptr(ws.rect), s)
+        call("post_nms", ptr(ws.score), ptr(ws.cls), ptr(ws.rect), B, A, self.nms_thre, 0, ptr(ws.skey), ptr(ws.sidx), ptr(ws.dead),
+             ptr(ws.keep), ptr(ws.count), ws.P, s)
+        rk = (B, A, str(pred.device))
+        row_off = _row_offs.get(rk)
+        if row_off is None:
+            row_off = _row_offs[rk] = _h2d(np.arange(B, dtype=np.int64) * A, pred.device)
+        self._match(lab, pred, ncols, row_off, ws.keep, A, ws.count, ws.conf, ws.cls, B, _pow2(A), B * A)
+
+    def update_detections(self, dets, labels):
+        """dets: list of B entries, None or [n, 29] (cx, cy, 24 radii, obj_conf, class_conf, class) as postprocess returns."""
+        B = len(dets)
+        if labels.shape[0] != B:
+            raise IndexError("%d detection entries, labels hold %d images" % (B, labels.shape[0]))
+        _lib.require_gpu()
+        dev = next((d.device for d in dets if d is not None), labels.device)
+        if dev.type != "cuda":
+            dev = torch.device("cuda", torch.cuda.current_device())
+        lab = self._prepare(labels, dev)
+        counts, parts = [], []
+        for d in dets:
+            if d is None or d.shape[0] == 0:
+                counts.append(0)
+                continue
+            if d.dim() != 2 or d.shape[1] != 29:
+                raise IndexError("expected detections [n, 29], got %s" % (tuple(d.shape),))
+            counts.append(int(d.shape[0]))
+            parts.append(d.detach().to(dev).float())
+        if B == 0:
+            return
+        if max(counts) > 65536:
+            raise Ep24Error("ep24: %d detections in one image: at most 65536 (EP24_E_UNSUPPORTED)" % max(counts))
+        N = sum(counts)
+        if N == 0:
+            rows = torch.zeros(1, 29, dtype=torch.float32, device=dev)
+        else:
+            rows = torch.cat(parts).contiguous()
+        off = np.zeros(B, dtype=np.int64)
+        off[1:] = np.cumsum(counts)[:-1]
+        row_off = _h2d(off, dev)
+        count = _h2d(np.array(counts, dtype=np.int32), dev)
+        self._match(lab, rows, 29, row_off, None, 0, count, None, None, B, _pow2(max(max(counts), 1)), max(N, 1))
+
+    def _match(self, lab, rows, ncols, row_off, keep, keep_stride, count, conf, cls, B, P, cap):
+        if self.seq + B > (1 << 25):
+            raise Ep24Error("ep24: more than 2^25 images in one evaluation (EP24_E_UNSUPPORTED)")
+        dev = rows.device
+        key = (B, P, cap, str(dev))
+        ms = _match_scratch.get(key)
+        if ms is None:
+            _match_scratch.clear()                        # one live shape at a time: an evaluation feeds batches of one size
+            ms = _match_scratch[key] = _MatchScratch(B, P, cap, dev)
+        ms.count.zero_()
+        cs, thr, _ = _device_consts(dev)
+        call("eval_match", ptr(lab), lab.shape[1], B, ptr(rows), ncols, ptr(row_off), ptr(keep), keep_stride, ptr(count), ptr(conf),
+             ptr(cls), self.num_classes, self._t, ptr(cs), ptr(thr), self.max_dets, self.seq, ptr(ms.sort), P, ptr(ms.key),
+             ptr(ms.cls), ptr(ms.p), ptr(ms.tp), ptr(ms.count), ptr(self._npig), ptr(self._err), stream_ptr())
+        n = int(ms.count.item())                          # the batch's one host synchronisation
+        if n:
+            self._recs.append((ms.key[:n].clone(), ms.cls[:n].clone(), ms.p[:n].clone(), ms.tp[:n].clone()))
+        self.n_records += n
+        self.seq += B
+
+    # ---- accumulation ------------------------------------------------------------------------------
+    def _sorted(self):
+        """The records of the evaluation sorted by (class, score desc, image seq, rank): (key, cls, p, tp, order) on the device."""
+        dev = self.device
+        if self._recs:
+            key = torch.cat([r[0] for r in self._recs])
+            cls = torch.cat([r[1] for r in self._recs])
+            p = torch.cat([r[2] for r in self._recs])
+            tp = torch.cat([r[3] for r in self._recs])
+        else:
+            key = torch.zeros(0, dtype=torch.int64, device=dev)
+            cls = p = tp = torch.zeros(0, dtype=torch.int32, device=dev)
+        n = key.numel()
+        order = torch.empty(n, dtype=torch.int32, device=dev)
+        if n:
+            if n > 0x7FFFFFFF:
+                raise Ep24Error("ep24: %d records: at most 2^31 - 1 (EP24_E_UNSUPPORTED)" % n)
+            key_tmp = torch.empty(2 * n, dtype=torch.int64, device=dev)
+            cls_tmp = torch.empty(2 * n, dtype=torch.int32, device=dev)
+            idx_tmp = torch.empty(2 * n, dtype=torch.int32, device=dev)
+            hist = torch.empty(256 * ((n + 4095) // 4096), dtype=torch.int32, device=dev)
+            low_bits = 7 + max(self.seq - 1, 0).bit_length()
+            cls_bits = max(self.num_classes - 1, 0).bit_length()
+            call("eval_sort", ptr(key), ptr(cls), n, low_bits, cls_bits, ptr(key_tmp), ptr(cls_tmp), ptr(idx_tmp), ptr(hist), ptr(order),
+                 stream_ptr())
+        return key, cls, p, tp, order
+
+    def records(self):
+        """Host copy of the sorted records: dict of numpy arrays cls, score (fp32), seq, rank, p, tp (10-bit masks)."""
+        if self._npig is None:
+            raise Ep24Error("ep24: no update() yet")
+        key, cls, p, tp, order = self._sorted()
+        o = order.long()
+        k = key[o].cpu().numpy().view(np.uint64)
+        sbits = (~(k >> np.uint64(32))).astype(np.uint32)
+        sbits = np.where(sbits & np.uint32(0x80000000), sbits & np.uint32(0x7FFFFFFF), ~sbits).astype(np.uint32)
+        return {"cls": cls[o].cpu().numpy(), "score": sbits.view(np.float32), "seq": ((k >> np.uint64(7)) & np.uint64((1 << 25) - 1)).astype(np.int64),
+                "rank": (k & np.uint64(127)).astype(np.int64), "p": p[o].cpu().numpy(), "tp": tp[o].cpu().numpy()}
+
+    def accumulate(self):
+        """-> (precision [10, 101, C], recall [10, C]) float64 numpy arrays: one device-to-host copy."""
+        if self._npig is None:
+            raise Ep24Error("ep24: no update() yet")
+        _lib.require_gpu()
+        dev, C = self.device, self.num_classes
+        key, cls, p, tp, order = self._sorted()
+        n = key.numel()
+        _, _, rthr = _device_consts(dev)
+        out = torch.empty(10 * 101 * C + 10 * C, dtype=torch.float64, device=dev)
+        rng = torch.empty(2 * C, dtype=torch.int64, device=dev)
+        ctp = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+        env = torch.empty(max(n, 1), dtype=torch.float64, device=dev)
+        call("eval_accumulate", ptr(order), ptr(cls), ptr(tp), n, ptr(self._npig), C, ptr(rthr), ptr(rng), ptr(ctp), ptr(env),
+             ptr(out), ptr(out, 10 * 101 * C), stream_ptr())
+        if int(self._err.item()):
+            raise Ep24Error("ep24: eval_match met an image with more detections than its scratch holds")
+        host = out.cpu().numpy()
+        return host[:10 * 101 * C].reshape(10, 101, C), host[10 * 101 * C:].reshape(10, C)
+
+    def summarize(self):
+        precision, recall = self.accumulate()
+        self.stats = summarize_tables(precision, recall)
+        self.stats["iou_type"] = self.iou_type
+        self.stats["images"] = self.seq
+        self.summary = format_summary(self.stats, self.max_dets)
+        return self.stats
+
+
+def _mean_valid(x):
+    v = x[x > -1]
+    return float(np.mean(v)) if v.size else -1.0
+
+
+def summarize_tables(precision, recall):
+    """pycocotools ``summarize`` for one area range and one maxDets: means over the entries > -1."""
+    return {"AP": _mean_valid(precision), "AP50": _mean_valid(precision[0]), "AP75": _mean_valid(precision[5]),
+            "AR100": _mean_valid(recall), "per_class_AP": np.array([_mean_valid(precision[:, :, k]) for k in range(precision.shape[2])]),
+            "precision": precision, "recall": recall}
+
+
+def format_summary(stats, max_dets=100):
+    lines = [" Average Precision  (AP) @[ IoU=0.50:0.95 | area=   all | maxDets=%3d ] = %.3f" % (max_dets, stats["AP"]),
+             " Average Precision  (AP) @[ IoU=0.50      | area=   all | maxDets=%3d ] = %.3f" % (max_dets, stats["AP50"]),
+             " Average Precision  (AP) @[ IoU=0.75      | area=   all | maxDets=%3d ] = %.3f" % (max_dets, stats["AP75"]),
+             " Average Recall     (AR) @[ IoU=0.50:0.95 | area=   all | maxDets=%3d ] = %.3f" % (max_dets, stats["AR100"])]
+    return "\n".join(lines) + "\n"

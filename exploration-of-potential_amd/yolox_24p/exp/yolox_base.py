@@ -45,6 +45,9 @@ class Exp(BaseExp):
         self.test_size = (640, 640)
         self.test_conf = 0.01
         self.nmsthre = 0.65
+        self.eval_len = 64               # images of the synthetic validation set (get_eval_loader)
+        self.eval_seed = 1               # its own seed: the training source uses 0
+        self.eval_iou_type = "circle24"  # ep24.evaluate: "circle24" (the model's geometry) or "rect" (bounding boxes)
 
     def get_model(self):
         from models import YOLOX, YOLOPAFPN, YOLOXHead
@@ -116,3 +119,50 @@ class Exp(BaseExp):
         from utils import LRScheduler
         return LRScheduler(self.scheduler, lr, iters_per_epoch, self.max_epoch, warmup_epochs=self.warmup_epochs,
                            warmup_lr_start=self.warmup_lr, no_aug_epochs=self.no_aug_epochs, min_lr_ratio=self.min_lr_ratio)
+
+    def get_eval_loader(self, batch_size, is_distributed=False, testdev=False, legacy=False):
+        """Raw uint8 validation batches (a ``SyntheticDataset`` with its own seed and ``eval_len`` images, in order, the last batch
+        may be short): ``eval`` letterboxes them on the GPU with ``TrainTransform.batch``.  Any loader yielding raw batches
+        ``(images, label rows, info, ids)`` can take its place."""
+        import torch
+        from datasets import SyntheticDataset, raw_collate
+        ds = SyntheticDataset(self.eval_len, tuple(self.test_size), self.synthetic_gts, self.num_classes, seed=self.eval_seed, raw=True)
+        # a generator of its own: iterating the loader must not draw from the global RNG the training run relies on
+        return torch.utils.data.DataLoader(ds, batch_size=batch_size, shuffle=False, num_workers=0, drop_last=False,
+                                           collate_fn=raw_collate, generator=torch.Generator())
+
+    def get_evaluator(self, batch_size, is_distributed=False, testdev=False, legacy=False):
+        """``ep24.evaluate.Evaluator24`` (COCO-style AP over 24-point detections, matching on the GPU) with ``test_conf`` /
+        ``nmsthre`` and the validation loader attached; the reference's signature (exp/yolox_base.py:199-214, commented out there)."""
+        from ep24._lib import Ep24Error
+        from ep24.evaluate import Evaluator24
+        if is_distributed:
+            raise Ep24Error("ep24: distributed evaluation (gathering records across ranks) is not implemented")
+        evaluator = Evaluator24(self.num_classes, iou_type=self.eval_iou_type, conf_thre=self.test_conf, nms_thre=self.nmsthre)
+        evaluator.dataloader = self.get_eval_loader(batch_size)
+        return evaluator
+
+    def eval(self, model, evaluator, is_distributed, half=False):
+        """Eval-mode forward of every validation batch, ``evaluator.update`` on the decoded predictions, ``summarize``.
+        Returns ``(ap50_95, ap50, summary)`` as stock YOLOX does; the model's training flag is restored."""
+        import torch
+        from ep24._lib import Ep24Error
+        from ep24.input import TrainTransform
+        if is_distributed:
+            raise Ep24Error("ep24: distributed evaluation (gathering records across ranks) is not implemented")
+        if half:
+            raise Ep24Error("ep24: the eval-mode network runs in bf16 with fp32 outputs; half=True is not a separate mode")
+        transform = TrainTransform(max_labels=50)
+        was_training = model.training
+        model.eval()
+        evaluator.reset()
+        try:
+            with torch.no_grad():
+                for images, targets, _, _ in evaluator.dataloader:
+                    imgs, labs = transform.batch(images, targets, tuple(self.test_size))
+                    evaluator.update(model(imgs, train=False), labs)
+            stats = evaluator.summarize()
+        finally:
+            if was_training:
+                model.train()
+        return stats["AP"], stats["AP50"], evaluator.summary

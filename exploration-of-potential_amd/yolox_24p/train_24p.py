@@ -41,6 +41,9 @@ class Trainer:
         self.start_device, self.numb_device = args.start_device, args.devices
         self.world = int(os.environ.get("WORLD_SIZE", 1))
         self.rank = int(os.environ.get("RANK", 0))
+        if getattr(args, "eval_interval", 0) and self.world > 1:
+            raise SystemExit("train_24p.py: --eval-interval under WORLD_SIZE=%d: distributed evaluation (gathering records across "
+                             "ranks) is not implemented; evaluate the saved checkpoints in a single-process run" % self.world)
         local = int(os.environ.get("LOCAL_RANK", args.start_device))
         dev = torch.device(args.device)
         if dev.type != "cuda":
@@ -207,6 +210,8 @@ class Trainer:
                 self.epoch_complete = True                # --steps ended the run exactly on the epoch's last iteration
             if self.rank == 0:
                 self.save_ckpt("last_epoch")
+            if args.eval_interval and self.epoch_complete and (epoch + 1) % args.eval_interval == 0:
+                self.evaluate_and_save_model()
             if done:
                 break
         if tp_t0 is not None:
@@ -232,6 +237,25 @@ class Trainer:
         self.check_ring_guard()
         if self.world > 1:
             torch.distributed.destroy_process_group()
+
+    def evaluate_and_save_model(self):
+        """COCO-style AP of the EMA model (--ema) or the model on the Exp's validation loader (exp.eval, ep24.evaluate), logged
+        and written to TensorBoard as val/COCOAP50 / val/COCOAP50_95; the best AP50:95 so far is saved as best_ckpt.pth.  Runs
+        between epochs: the eval-mode plans and folded weights are separate buffers, so the captured step replays unchanged."""
+        if getattr(self, "evaluator", None) is None:
+            self.evaluator = self.exp.get_evaluator(self.args.batch_size)
+            self.best_ap = -1.0
+        model = self.ema_model.ema if self.ema_model is not None else self.model
+        ap50_95, ap50, summary = self.exp.eval(model, self.evaluator, False)
+        self.model.train()
+        if self.rank == 0:
+            print("eval epoch %d  AP50_95 %.4f  AP50 %.4f  (%d images)\n%s" % (self.epoch + 1, ap50_95, ap50, self.evaluator.seq, summary))
+            if self.tblogger is not None:
+                self.tblogger.add_scalar("val/COCOAP50", ap50, self.epoch + 1)
+                self.tblogger.add_scalar("val/COCOAP50_95", ap50_95, self.epoch + 1)
+            is_best = ap50_95 > self.best_ap
+            self.best_ap = max(self.best_ap, ap50_95)
+            self.save_ckpt("last_epoch", update_best_ckpt=is_best)
 
     @staticmethod
     def ring_timeouts():
@@ -342,6 +366,8 @@ def make_parser():
     p.add_argument("--throughput-json", default=None, type=str, help="with --steps N: write images/s over the run's last --throughput-window steps "
                    "(synchronised at both ends) to this file")
     p.add_argument("--throughput-window", default=200, type=int)
+    p.add_argument("--eval-interval", default=0, type=int, help="every N epochs: COCO-style AP (exp.eval, ep24.evaluate) of the EMA model "
+                   "(--ema) or the model, logged and saved as best_ckpt.pth when it improves (0 = off; single process only)")
     return p
 
 

@@ -531,6 +531,39 @@ int ep24_post_gather(const float* pred, int ncols, const float* conf, const int3
                      float* det, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * E1  evaluation: COCO-style AP of 24-point detections (pycocotools evaluateImg + accumulate, area "all", no crowd /
+ *     ignore, one maxDets; csrc/evaluate.hip).  iou_type 0 = circle24 (mean over the 24 rays of the ray circles' IoU,
+ *     fp32), 1 = rect (axis-aligned boxes, float64).  ray_cs[48] = cos(15 deg * k), then sin(15 deg * k), fp32.
+ * ------------------------------------------------------------------------------------------------ */
+/* out[G][D] double = IoU of gt50[G][50] (centre + 24 vertices, label columns 1..50) against det26[D][26] (centre + 24 radii). */
+int ep24_eval_iou(const float* gt50, const float* det26, int G, int D, int iou_type, const float* ray_cs, double* out,
+                  void* stream);
+/* One workgroup per image b of labels[B][L][51] (L <= 256; the first n rows, n = rows whose sum is > 0).  Detection r < count[b]
+ * of image b is row row_off[b] + a of rows[.][ncols], a = keep[b * keep_stride + r] (keep nullable: a = r); class_conf / class
+ * from conf / cls at that row index (post_prepare's arrays) or, both null, from the row's columns 27 / 28 (postprocess rows).
+ * score = row[26] * class_conf.  Per (image, class) the first max_dets (<= 128) detections in (score desc, r asc) order are
+ * matched greedily at the 10 thresholds iou_thr[10] (double, compared against min(t, 1 - 1e-10); equal IoUs go to the later GT
+ * row); each appends one record at an offset taken from *rec_count: rec_key = (~ordered score bits) << 32 | (seq_base + b) << 7
+ * | rank, rec_cls, rec_p = r, rec_tp = 10-bit TP mask.  npig[num_classes] += the GTs per class.  sort_scratch [B][P] int64
+ * (P a power of two >= every count, <= 65536); *err |= 1 if a count exceeds P.  num_classes < 65535, seq_base + B <= 2^25. */
+int ep24_eval_match(const float* labels, int L, int B, const float* rows, int ncols, const int64_t* row_off,
+                    const int32_t* keep, int64_t keep_stride, const int32_t* count, const float* conf, const int32_t* cls,
+                    int num_classes, int iou_type, const float* ray_cs, const double* iou_thr, int max_dets,
+                    int64_t seq_base, int64_t* sort_scratch, int P, int64_t* rec_key, int32_t* rec_cls, int32_t* rec_p,
+                    int32_t* rec_tp, int32_t* rec_count, int32_t* npig, int32_t* err, void* stream);
+/* Stable LSD radix sort of n records by (class, key): order[n] = record indices in that order.  Passes of 8 bits over the
+ * key's low key_low_bits bits, its high 32 bits and the class's low cls_bits bits.  Scratch: key_tmp [2][n], cls_tmp [2][n],
+ * idx_tmp [2][n], hist [256 * ceil(n / 4096)]. */
+int ep24_eval_sort(const int64_t* key, const int32_t* cls, int64_t n, int key_low_bits, int cls_bits, int64_t* key_tmp,
+                   int32_t* cls_tmp, int32_t* idx_tmp, int32_t* hist, int32_t* order, void* stream);
+/* One workgroup per class over the sorted records: precision[10][101][num_classes] and recall[10][num_classes] (double) as
+ * pycocotools accumulate computes them, -1 for a class without GTs.  rec_thr[101] double; cls_range [num_classes][2] int64,
+ * ctp_scratch [n] int32, env_scratch [n] double. */
+int ep24_eval_accumulate(const int32_t* order, const int32_t* rec_cls, const int32_t* rec_tp, int64_t n, const int32_t* npig,
+                         int num_classes, const double* rec_thr, int64_t* cls_range, int32_t* ctp_scratch,
+                         double* env_scratch, double* precision, double* recall, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * N4  24-point label generation (yolox_24p/datasets/2+24_labels_create.py:61-116, :175-180)
  * ------------------------------------------------------------------------------------------------ */
 /* rotation_for_24p for n objects (n <= 65535 per call).  masks: uint8 instance masks (non-zero = object) somewhere in
