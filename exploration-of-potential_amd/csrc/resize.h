@@ -4,10 +4,8 @@
 #pragma once
 #include "common.h"
 
-// scale is OpenCV's double 1 / (dsize / ssize) (cv::hal::resize: inv_scale = (double)dsize/ssize, scale = 1./inv_scale;
-// the coefficient loop rounds (d + 0.5)*scale - 0.5 to float)
-__device__ __forceinline__ void lin_coef(int d, double scale, int ssize, int& s0, int& s1, int& a0, int& a1) {
-    float f = (float)((d + 0.5) * scale - 0.5);
+// coefficients of the float source coordinate f (the affine sampler of augment.hip hands over its own)
+__device__ __forceinline__ void lin_coef_at(float f, int ssize, int& s0, int& s1, int& a0, int& a1) {
     int s = (int)floorf(f);
     f -= (float)s;
     if (s < 0) { f = 0.f; s = 0; }
@@ -16,6 +14,12 @@ __device__ __forceinline__ void lin_coef(int d, double scale, int ssize, int& s0
     s1 = s + 1 < ssize ? s + 1 : ssize - 1;
     a0 = (int)rintf((1.f - f) * 2048.f);
     a1 = (int)rintf(f * 2048.f);
+}
+
+// scale is OpenCV's double 1 / (dsize / ssize) (cv::hal::resize: inv_scale = (double)dsize/ssize, scale = 1./inv_scale;
+// the coefficient loop rounds (d + 0.5)*scale - 0.5 to float)
+__device__ __forceinline__ void lin_coef(int d, double scale, int ssize, int& s0, int& s1, int& a0, int& a1) {
+    lin_coef_at((float)((d + 0.5) * scale - 0.5), ssize, s0, s1, a0, a1);
 }
 
 __device__ __forceinline__ int lin_mix_u8(int p00, int p01, int p10, int p11, int ax0, int ax1, int by0, int by1) {

@@ -1,0 +1,265 @@
+"""Training augmentation on the GPU for 24-point labels: mosaic, random affine, mirror, HSV (csrc/augment.hip).
+
+The reference's 24p ``TrainTransform`` accepts ``flip_prob`` / ``hsv_prob`` and ignores them, and its mosaic /
+``random_affine`` code (yolox_24p/data/) transforms boxes only.  Here the raw uint8 images that the prefetcher uploads
+anyway are sampled straight into the network input through the inverse affine map, and every 24-point polygon is mapped
+forward and its 24 rays are re-cast from the new centre (``ep24_augment_labels``).
+
+``sample_params`` draws what stock YOLOX draws (``MosaicDetection.__getitem__``, ``get_affine_matrix``, ``_mirror``,
+``augment_hsv``); ``mosaic_batch`` runs the two launches on explicit parameters; ``MosaicTransform`` is the
+``TrainTransform`` that a ``DataPrefetcher`` takes.  Deviations from the reference, on purpose: the three mosaic partners of
+an image come from the SAME BATCH (the reference draws them from the whole dataset; here nothing extra is uploaded), and
+mixup is not implemented.  There is no CPU fallback.
+"""
+import math
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import call, ptr, stream_ptr
+from .input import TrainTransform, letterbox_geometry
+
+HSV_GAINS = (5.0, 30.0, 30.0)         # augment_hsv's hgain, sgain, vgain
+
+
+def affine_inverse(M):
+    """Inverse of o = A c + t as the kernels take it: [[i00, i01, i02], [i10, i11, i12]] in double."""
+    a00, a01, t0, a10, a11, t1 = (float(v) for v in np.asarray(M, dtype=np.float64).reshape(6))
+    det = a00 * a11 - a01 * a10
+    if det == 0.0:
+        raise ValueError("singular affine matrix")
+    i00, i01, i10, i11 = a11 / det, -a01 / det, -a10 / det, a00 / det
+    return np.array([[i00, i01, -(i00 * t0 + i01 * t1)], [i10, i11, -(i10 * t0 + i11 * t1)]], dtype=np.float64)
+
+
+def affine_matrix(angle, scale, shear_x, shear_y, tx, ty):
+    """``get_affine_matrix``'s matrix: rotation by ``angle`` degrees about the origin times ``scale``
+    (cv2.getRotationMatrix2D's convention: [[a, b], [-b, a]], a = scale*cos, b = scale*sin), then the two shears (degrees),
+    then the translation in output pixels."""
+    a, b = scale * math.cos(math.radians(angle)), scale * math.sin(math.radians(angle))
+    r0, r1 = (a, b), (-b, a)
+    kx, ky = math.tan(math.radians(shear_x)), math.tan(math.radians(shear_y))
+    return np.array([[r0[0] + ky * r1[0], r0[1] + ky * r1[1], tx],
+                     [r1[0] + kx * r0[0], r1[1] + kx * r0[1], ty]], dtype=np.float64)
+
+
+class AugParams:
+    """Explicit parameters of one batch of n output images: ``mosaic`` bool [n]; ``centre`` int [n,2] = (xc, yc) on the
+    2S canvas; ``partners`` int [n,4] = source index of the top-left, top-right, bottom-left, bottom-right tile (column 0
+    is the image itself); ``M`` float64 [n,2,3] canvas -> output and ``Minv`` its inverse; ``mirror`` bool [n];
+    ``hsv_on`` bool [n]; ``hsv`` float64 [n,3] = gains (dh, ds, dv).  Without mosaic an image is its own single tile,
+    letterboxed at the top left of an S canvas, and ``M`` is whatever the caller sets (``sample_params``: identity)."""
+
+    def __init__(self, n):
+        self.n = n
+        self.mosaic = np.zeros(n, dtype=bool)
+        self.centre = np.zeros((n, 2), dtype=np.int64)
+        self.partners = np.tile(np.arange(n, dtype=np.int64)[:, None], (1, 4))
+        self.M = np.tile(np.array([[1.0, 0.0, 0.0], [0.0, 1.0, 0.0]]), (n, 1, 1))
+        self.Minv = self.M.copy()
+        self.mirror = np.zeros(n, dtype=bool)
+        self.hsv_on = np.zeros(n, dtype=bool)
+        self.hsv = np.zeros((n, 3), dtype=np.float64)
+
+    def set_matrix(self, i, M):
+        self.M[i] = np.asarray(M, dtype=np.float64).reshape(2, 3)
+        self.Minv[i] = affine_inverse(self.M[i])
+
+
+def identity_params(n):
+    """Parameters that make ``mosaic_batch`` the plain ``TrainTransform``."""
+    return AugParams(n)
+
+
+def position_rng(seed, epoch, it):
+    """The generator of batch (epoch, it) of a run seeded with ``seed``."""
+    return np.random.RandomState(np.array([seed, epoch, it], dtype=np.uint32))
+
+
+def sample_params(rng, sizes, input_size, mosaic_prob=1.0, degrees=10.0, translate=0.1, mosaic_scale=(0.5, 1.5), shear=2.0,
+                  flip_prob=0.5, hsv_prob=1.0):
+    """Draws the parameters of ``len(sizes)`` output images from ``rng`` (a ``np.random.RandomState``).
+
+    Per output image, in this order and ALWAYS all 20 numbers (what a coin switches off is drawn and dropped, so the
+    parameters of image i depend on the generator's state and i only):
+      1  u_mosaic  = random_sample()              mosaic if u_mosaic < mosaic_prob
+      2  yc        = int(uniform(0.5 S_h, 1.5 S_h))
+      3  xc        = int(uniform(0.5 S_w, 1.5 S_w))
+      4-6 partners = randint(0, n) three times    (top-right, bottom-left, bottom-right; same batch)
+      7  angle     = uniform(-degrees, degrees)
+      8  scale     = uniform(*mosaic_scale)
+      9  shear_x, 10 shear_y = uniform(-shear, shear)
+      11 tx = uniform(-translate, translate) * S_w, 12 ty = ... * S_h
+      13 u_mirror  = random_sample()              mirror if u_mirror < flip_prob
+      14 u_hsv     = random_sample()              HSV if u_hsv < hsv_prob
+      15-17 gains  = uniform(-1, 1) * (5, 30, 30), 18-20 switches = randint(0, 2); gain * switch truncated to an integer
+    Without mosaic the matrix is the identity (stock YOLOX applies mirror and HSV only to such an image)."""
+    n = len(sizes)
+    S_h, S_w = int(input_size[0]), int(input_size[1])
+    p = AugParams(n)
+    for i in range(n):
+        u_mosaic = rng.random_sample()
+        yc = int(rng.uniform(0.5 * S_h, 1.5 * S_h))
+        xc = int(rng.uniform(0.5 * S_w, 1.5 * S_w))
+        partners = [int(rng.randint(0, n)) for _ in range(3)]
+        angle = rng.uniform(-degrees, degrees)
+        scale = rng.uniform(mosaic_scale[0], mosaic_scale[1])
+        shear_x, shear_y = rng.uniform(-shear, shear), rng.uniform(-shear, shear)
+        tx, ty = rng.uniform(-translate, translate) * S_w, rng.uniform(-translate, translate) * S_h
+        u_mirror, u_hsv = rng.random_sample(), rng.random_sample()
+        gains = [rng.uniform(-1.0, 1.0) * g for g in HSV_GAINS]
+        switches = [int(rng.randint(0, 2)) for _ in range(3)]
+        if u_mosaic < mosaic_prob:
+            p.mosaic[i] = True
+            p.centre[i] = (xc, yc)
+            p.partners[i, 1:] = partners
+            p.set_matrix(i, affine_matrix(angle, scale, shear_x, shear_y, tx, ty))
+        p.mirror[i] = u_mirror < flip_prob
+        p.hsv_on[i] = u_hsv < hsv_prob
+        p.hsv[i] = [float(int(g * s)) for g, s in zip(gains, switches)]
+    return p
+
+
+def tile_layout(params, i, sizes, input_size):
+    """The tiles of output image i: list of (source index, rw, rh, (lx1, ly1, lx2, ly2), padw, padh).  Mosaic: quadrant q
+    (bit 0 = right, bit 1 = bottom) holds its source, resized to (rw, rh), with the corner that touches the mosaic centre
+    (xc, yc) pinned there and the far side cropped at the 2S canvas - the placement of the reference's mosaic."""
+    S_h, S_w = int(input_size[0]), int(input_size[1])
+    out = []
+    if not params.mosaic[i]:
+        h, w = sizes[i]
+        _, rh, rw = letterbox_geometry(h, w, (S_h, S_w))
+        return [(i, rw, rh, (0, 0, rw, rh), 0, 0)]
+    xc, yc = int(params.centre[i][0]), int(params.centre[i][1])
+    for q in range(4):
+        j = int(params.partners[i][q])
+        h, w = sizes[j]
+        _, rh, rw = letterbox_geometry(h, w, (S_h, S_w))
+        if q & 1:
+            lx1, lx2, padw = xc, min(xc + rw, 2 * S_w), xc
+        else:
+            lx1, lx2, padw = max(xc - rw, 0), xc, xc - rw
+        if q & 2:
+            ly1, ly2, padh = yc, min(yc + rh, 2 * S_h), yc
+        else:
+            ly1, ly2, padh = max(yc - rh, 0), yc, yc - rh
+        out.append((j, rw, rh, (lx1, ly1, lx2, ly2), padw, padh))
+    return out
+
+
+_ROT = {}
+
+
+def _rot(dev):
+    from .labels24 import _rot_table
+    if dev not in _ROT:
+        _ROT[dev] = _rot_table(dev).clone()
+    return _ROT[dev]
+
+
+def mosaic_batch(images, targets, params, input_size, max_labels=50, out_images=None, out_labels=None, min_margin=2.0,
+                 device="cuda:0"):
+    """images: list of uint8 [h,w,3] arrays / tensors; targets: list of [k,51] normalised label rows; params: ``AugParams``.
+    Returns (images [n,3,S_h,S_w] fp32, labels [n,max_labels,51] fp32, survivors per image [n] int32) on the device."""
+    _lib.require_gpu()
+    n = len(images)
+    if params.n != n or len(targets) != n:
+        raise ValueError("mosaic_batch: %d images, %d label tables, parameters for %d" % (n, len(targets), params.n))
+    S_h, S_w = int(input_size[0]), int(input_size[1])
+    dev = out_images.device if out_images is not None else torch.device(device)
+    if out_images is None:
+        out_images = torch.empty(n, 3, S_h, S_w, dtype=torch.float32, device=dev)
+    if out_labels is None:
+        out_labels = torch.empty(n, max_labels, 51, dtype=torch.float32, device=dev)
+    counts = torch.empty(n, dtype=torch.int32, device=dev)
+    if n == 0:
+        return out_images, out_labels, counts
+    flat, offs, sizes, off = [], [], [], 0
+    for im in images:
+        im = im if isinstance(im, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(im))
+        if im.dim() != 3 or im.shape[2] != 3 or im.dtype != torch.uint8 or im.shape[0] == 0 or im.shape[1] == 0:
+            raise ValueError("mosaic_batch takes uint8 [h,w,3] images")
+        h, w = int(im.shape[0]), int(im.shape[1])
+        flat.append(im.reshape(-1))
+        offs.append(off)
+        sizes.append((h, w))
+        off += h * w * 3
+    rows, row_off = [], [0]
+    for t in targets:
+        t = np.asarray(t, dtype=np.float64)
+        t = t.reshape(-1, 51) if t.size else np.zeros((0, 51))
+        rows.append(t)
+        row_off.append(row_off[-1] + t.shape[0])
+    tiles = np.zeros((n, 4, 16), dtype=np.int64)
+    # doubles in one upload: tile scales [n,4,3], parameters [n,16], label rows [R,51]
+    dbl = np.zeros(n * 12 + n * 16 + max(row_off[-1], 1) * 51, dtype=np.float64)
+    tsc, par = dbl[:n * 12].reshape(n, 4, 3), dbl[n * 12:n * 28].reshape(n, 16)
+    if row_off[-1]:
+        dbl[n * 28:] = np.concatenate(rows, 0).reshape(-1)
+    flags = np.zeros((n, 2), dtype=np.int32)
+    for i in range(n):
+        for q, (j, rw, rh, (lx1, ly1, lx2, ly2), padw, padh) in enumerate(tile_layout(params, i, sizes, (S_h, S_w))):
+            h, w = sizes[j]
+            if rw <= 0 or rh <= 0 or lx2 <= lx1 or ly2 <= ly1:
+                continue                                                       # nothing of this tile is on the canvas
+            tiles[i, q, :14] = (offs[j], h, w, 3 * w, rw, rh, lx1, ly1, lx2, ly2, padw, padh, row_off[j], row_off[j + 1])
+            tsc[i, q] = (1.0 / (rw / w), 1.0 / (rh / h), min(S_h / h, S_w / w))
+        par[i, 0:6] = params.M[i].reshape(6)
+        par[i, 6:12] = params.Minv[i].reshape(6)
+        par[i, 12:15] = params.hsv[i]
+        flags[i] = (int(params.mirror[i]), int(params.hsv_on[i]))
+    if not (np.isfinite(par).all() and np.isfinite(tsc).all()):
+        raise ValueError("mosaic_batch: non-finite parameters")
+    buf = torch.cat([f.to(dev, non_blocking=True) for f in flat])
+    tiles_t = torch.from_numpy(tiles).to(dev)
+    dbl_t = torch.from_numpy(dbl).to(dev)
+    flags_t = torch.from_numpy(flags).to(dev)
+    rot = _rot(dev)
+    for lo in range(0, n, 65535):
+        hi = min(n, lo + 65535)
+        call("augment_u8", ptr(buf), ptr(tiles_t, lo * 64), ptr(dbl_t, lo * 12), ptr(dbl_t, n * 12 + lo * 16), ptr(flags_t, lo * 2),
+             hi - lo, ptr(out_images, lo * 3 * S_h * S_w), S_h, S_w, stream_ptr())
+    call("augment_labels", ptr(dbl_t, n * 28), ptr(tiles_t), ptr(dbl_t), ptr(dbl_t, n * 12), ptr(flags_t), ptr(rot), n, S_h, S_w,
+         float(min_margin), ptr(out_labels), ptr(counts), max_labels, stream_ptr())
+    return out_images, out_labels, counts
+
+
+class MosaicTransform(TrainTransform):
+    """``TrainTransform`` with the augmentation switched on: same ``batch(...)`` signature, so ``DataPrefetcher`` takes it
+    unchanged.  ``enabled = False`` makes it the plain transform (the last ``no_aug_epochs`` of a YOLOX run).
+    ``set_position(epoch, it)`` reseeds the generator from (seed, epoch, it): the batch at a data position gets the same
+    parameters whenever it is produced, so a resumed run reproduces the batches it would have seen."""
+
+    def __init__(self, max_labels=50, flip_prob=0.5, hsv_prob=1.0, mosaic_prob=1.0, degrees=10.0, translate=0.1,
+                 mosaic_scale=(0.5, 1.5), shear=2.0, min_margin=2.0, seed=0, enabled=True):
+        super().__init__(max_labels=max_labels, flip_prob=flip_prob, hsv_prob=hsv_prob, seed=seed)
+        self.hsv_prob, self.mosaic_prob, self.degrees, self.translate = hsv_prob, mosaic_prob, degrees, translate
+        self.mosaic_scale, self.shear, self.min_margin = tuple(mosaic_scale), shear, min_margin
+        self.seed, self.enabled = int(seed), enabled
+        self.last_params = self.last_counts = None
+        self.set_position(0, 0)
+
+    @classmethod
+    def from_exp(cls, exp, max_labels=50, seed=0):
+        return cls(max_labels=max_labels, flip_prob=exp.flip_prob, hsv_prob=exp.hsv_prob, mosaic_prob=exp.mosaic_prob,
+                   degrees=exp.degrees, translate=exp.translate, mosaic_scale=exp.mosaic_scale, shear=exp.shear, seed=seed)
+
+    def set_position(self, epoch, it):
+        self.position = (int(epoch), int(it))
+        self._aug_rng = position_rng(self.seed, epoch, it)
+
+    def sample(self, sizes, input_dim):
+        return sample_params(self._aug_rng, sizes, input_dim, mosaic_prob=self.mosaic_prob, degrees=self.degrees,
+                             translate=self.translate, mosaic_scale=self.mosaic_scale, shear=self.shear,
+                             flip_prob=self.flip_prob, hsv_prob=self.hsv_prob)
+
+    def batch(self, images, targets, input_dim, out_images=None, out_labels=None):
+        if not self.enabled:
+            return super().batch(images, targets, input_dim, out_images=out_images, out_labels=out_labels)
+        _lib.require_gpu()
+        params = self.sample([tuple(im.shape[:2]) for im in images], input_dim)
+        imgs, labs, counts = mosaic_batch(images, targets, params, input_dim, self.max_labels, out_images, out_labels,
+                                          min_margin=self.min_margin)
+        self.last_params, self.last_counts = params, counts
+        return imgs, labs

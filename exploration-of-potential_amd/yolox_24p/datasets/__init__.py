@@ -74,3 +74,4 @@ COCO24PDataset = SyntheticDataset        # name the reference's Exp imports (exp
 
 
 from ep24.input import TrainTransform, preproc  # noqa: E402,F401   (datasets/data_augment.py:109-174, on the GPU)
+from ep24.augment import MosaicTransform  # noqa: E402,F401   (mosaic / affine / mirror / HSV for 24-point labels, on the GPU)

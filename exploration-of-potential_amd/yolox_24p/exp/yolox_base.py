@@ -26,6 +26,14 @@ class Exp(BaseExp):
         self.synthetic_len = 64          # images per synthetic epoch
         self.loader_workers = 4          # processes of the synthetic fp32 loader (train_24p.py --loader-workers)
         self.synthetic_gts = 10
+        # augmentation (stock YOLOX's names and values; read by train_24p.py --augment only: ep24.augment.MosaicTransform)
+        self.mosaic_prob = 1.0
+        self.degrees = 10.0
+        self.translate = 0.1
+        self.mosaic_scale = (0.5, 1.5)
+        self.shear = 2.0
+        self.flip_prob = 0.5
+        self.hsv_prob = 1.0
         # training
         self.warmup_epochs = 5
         self.max_epoch = 300

@@ -68,6 +68,8 @@ class Trainer:
         if args.raw_u8 and (args.no_prefetch or args.fp32_batches):
             raise SystemExit("train_24p.py: --raw-u8 batches are letterboxed by the prefetcher (drop --no-prefetch / --fp32-batches)")
         args.raw_u8 = not (args.fp32_batches or args.no_prefetch)
+        if args.augment and not args.raw_u8:
+            raise SystemExit("train_24p.py: --augment works on the raw uint8 batches behind the prefetcher (drop --no-prefetch / --fp32-batches)")
         self.train_loader = exp.get_data_loader(args.batch_size, raw_u8=bool(args.raw_u8), workers=args.loader_workers,
                                                  pin=None if args.loader_pin is None else bool(args.loader_pin))
         self.loss_func = Loss_Function(exp.num_classes)
@@ -288,7 +290,10 @@ class Trainer:
                 yield images.to(self.device, non_blocking=True), labels.to(self.device, non_blocking=True)
             return
         from ep24.input import DataPrefetcher, TrainTransform
-        pf = DataPrefetcher(self.train_loader, tuple(self.input_size), TrainTransform(max_labels=50))
+        if self.args.augment:
+            pf = DataPrefetcher(self.positioned(self.train_loader), tuple(self.input_size), self.augment_transform())
+        else:
+            pf = DataPrefetcher(self.train_loader, tuple(self.input_size), TrainTransform(max_labels=50))
         self.prefetcher = pf                              # its t_loader / t_upload split the throughput record's host time
         if self.args.resident_batch:                      # diagnostic: what the input pipeline costs the GPU (tools/trainer_timing.sh)
             images, labels = pf.next()
@@ -300,6 +305,25 @@ class Trainer:
             if images is None:
                 return
             yield images, labels
+
+    def augment_transform(self):
+        """--augment: ONE ``MosaicTransform`` for the run (the Exp's mosaic_prob / degrees / translate / mosaic_scale / shear /
+        flip_prob / hsv_prob), switched on for epochs < max_epoch - no_aug_epochs and off after - what ``no_aug_epochs`` means in
+        YOLOX (core/trainer.py before_epoch: close_mosaic)."""
+        if getattr(self, "transform", None) is None:
+            from datasets import MosaicTransform
+            self.transform = MosaicTransform.from_exp(self.exp, max_labels=50, seed=self.args.augment_seed)
+        self.transform.enabled = self.epoch < self.max_epoch - self.exp.no_aug_epochs
+        return self.transform
+
+    def positioned(self, loader):
+        """The loader's raw batches, each one behind ``set_position(epoch, iteration of the epoch)``: the prefetcher transforms a
+        batch right after it has drawn it, so every batch gets the parameters of its own data position (also in a resumed epoch,
+        whose first batches the sampler leaves out)."""
+        first = getattr(loader.sampler, "start", 0) // max(self.args.batch_size, 1)
+        for it, batch in enumerate(loader, first):
+            self.transform.set_position(self.epoch, it)
+            yield batch
 
     def TB_data(self, res, ips):
         """One D2H copy of the packed result vector: [0] loss, [1..24] weighted IOU losses, [25] conf, [26] cls,
@@ -366,6 +390,10 @@ def make_parser():
     p.add_argument("--throughput-json", default=None, type=str, help="with --steps N: write images/s over the run's last --throughput-window steps "
                    "(synchronised at both ends) to this file")
     p.add_argument("--throughput-window", default=200, type=int)
+    p.add_argument("--augment", action="store_true", help="mosaic, random affine, mirror and HSV on the GPU for 24-point labels (ep24.augment."
+                   "MosaicTransform behind the prefetcher) with the Exp's mosaic_prob / degrees / translate / mosaic_scale / shear / flip_prob / "
+                   "hsv_prob, for epochs < max_epoch - no_aug_epochs")
+    p.add_argument("--augment-seed", default=0, type=int, help="seed of the augmentation; a batch's parameters follow from (seed, epoch, iteration)")
     p.add_argument("--eval-interval", default=0, type=int, help="every N epochs: COCO-style AP (exp.eval, ep24.evaluate) of the EMA model "
                    "(--ema) or the model, logged and saved as best_ckpt.pth when it improves (0 = off; single process only)")
     return p

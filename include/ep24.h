@@ -592,6 +592,38 @@ int ep24_preproc_u8(const uint8_t* images, const int64_t* desc, const double* sc
 int ep24_preproc_labels(const double* rows, const int64_t* row_off, const double* whr, int n, float* out, int max_labels,
                         void* stream);
 
+/* Training augmentation (mosaic, random affine, mirror, HSV), two launches per batch.  Every output image
+ * is assembled from up to four TILES: a tile is one source image, resized by s = min(S_h/h, S_w/w) as preproc resizes it and
+ * placed on a canvas (2 S_h x 2 S_w with four tiles for a mosaic; S_h x S_w with one tile at the top left without).  Shared inputs:
+ *   tiles[n][4][16] int64 = {0 byte offset of the source in `images`, 1 h, 2 w, 3 row stride in bytes, 4 rw = int(w*s),
+ *       5 rh = int(h*s), 6 lx1, 7 ly1, 8 lx2, 9 ly2 (canvas region [lx1,lx2) x [ly1,ly2)), 10 padw, 11 padh (canvas position of
+ *       the resized image's pixel (0,0): lx1 - sx1, ly1 - sy1), 12 row_lo, 13 row_hi (the source's label rows in `rows`),
+ *       14, 15 reserved (0)}; an unused tile has an empty region (lx2 == lx1) and row_hi == row_lo;
+ *   tile_scales[n][4][3] double = {1/(rw/w), 1/(rh/h) (OpenCV's scale_x, scale_y, as for ep24_preproc_u8), s};
+ *   params[n][16] double = {0 a00, 1 a01, 2 t0, 3 a10, 4 a11, 5 t1: canvas -> output, o = A*c + t;  6 i00, 7 i01, 8 i02, 9 i10,
+ *       10 i11, 11 i12: its inverse, computed by the host in double;  12 dh, 13 ds, 14 dv: HSV gains;  15 reserved (0)};
+ *   flags[n][2] int32 = {mirror, hsv on}.
+ * ep24_augment_u8: out [n,3,S_h,S_w] fp32.  Output pixel (x, y): xm = mirror ? S_w-1-x : x; canvas u = (i00*xm + i01*y) + i02,
+ * v = (i10*xm + i11*y) + i12 in double; the owner is the first tile with lx1-0.5 <= u < lx2-0.5 and ly1-0.5 <= v < ly2-0.5 (none:
+ * 114 in the three channels); fx = ((u - padw) + 0.5)*scale_x - 0.5 (fy likewise) in double, rounded to float, then the fixed-point
+ * bilinear sample of ep24_preproc_u8.  With hsv on, sampled pixels (not the padding) go BGR -> HSV (H in [0,180), S, V in [0,255]),
+ * H = (H + dh) mod 180, S = clip(S + ds, 0, 255), V = clip(V + dv, 0, 255) and back in fp32, nothing rounded to uint8 (cv2 rounds
+ * twice).  With hsv off the output is a bit-exact function of the inputs. */
+int ep24_augment_u8(const uint8_t* images, const int64_t* tiles, const double* tile_scales, const double* params,
+                    const int32_t* flags, int n, float* out, int S_h, int S_w, void* stream);
+/* The label half: rows [total][51] double = (class, 50 normalised coordinates); rot[24][2] double = cos / sin of k*15 degrees
+ * (ep24.labels24._rot_table).  Candidates of image i are the rows of tile 0, then tile 1, ... (the first max_labels of each).
+ * All arithmetic in double: canvas X = (v*w)*s + padw, Y = (v*h)*s + padh; output c' = A*c + t, P'_j = A*P_j + t, mirrored
+ * x -> S_w - x.  A candidate survives if its centre is at least min_margin inside both the output rectangle [0,S_w] x [0,S_h] and
+ * (in canvas space) its tile's region, and if the 24 re-cast vertices have min(width, height) > 1.  Re-cast vertex k =
+ * c' + r_k * (cos, sin)(15k deg), r_k = the smallest t >= 0 at which the ray meets one of the 24 edges P'_j -> P'_j+1 (ends
+ * included), cut at the ray's exit from the output rectangle and at its exit from the tile's region (taken in canvas space along
+ * A^-1 * d, x negated first when mirrored).  out [n][max_labels][51] fp32: the survivors in candidate order, the first max_labels
+ * of them, zero padded; out_count[n] int32: the number of survivors (it may exceed max_labels). */
+int ep24_augment_labels(const double* rows, const int64_t* tiles, const double* tile_scales, const double* params,
+                        const int32_t* flags, const double* rot, int n, int S_h, int S_w, double min_margin, float* out,
+                        int32_t* out_count, int max_labels, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * C4  swapped backbones (yolox_24p/models/darknet.py:179-429, yolox/models/yolo_pafpn.py:31-38; BASELINE config 4)
  *     The conv / BN+act entry points above carry them (act = 2 is ReLU); these are the remaining pieces.
