@@ -265,11 +265,13 @@ __device__ __forceinline__ void igemm_epilogue(const IgemmArgs& p, f32x4 (&acc)[
                             v[q] = y;
                         }
                 }
+                // accumulate: bf16(float(bf16(acc)) + old), the expression of the 16-byte store path above (which adds to the staged,
+                // already rounded tile) - the store width must not change a bit of the result
                 if (c0 + 3 < p.N) {
                     if (p.accumulate) {
                         bf16x4 o = *reinterpret_cast<const bf16x4*>(d);
 #pragma unroll
-                        for (int q = 0; q < 4; ++q) v[q] += (float)o[q];
+                        for (int q = 0; q < 4; ++q) v[q] = (float)(bf16)v[q] + (float)o[q];
                     }
                     bf16x4 w;
 #pragma unroll
@@ -278,7 +280,7 @@ __device__ __forceinline__ void igemm_epilogue(const IgemmArgs& p, f32x4 (&acc)[
                 } else {
 #pragma unroll
                     for (int q = 0; q < 4; ++q)
-                        if (c0 + q < p.N) d[q] = (bf16)(p.accumulate ? (float)d[q] + v[q] : v[q]);
+                        if (c0 + q < p.N) d[q] = (bf16)(p.accumulate ? (float)d[q] + (float)(bf16)v[q] : v[q]);
                 }
             }
         }

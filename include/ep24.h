@@ -57,7 +57,9 @@ int ep24_conv_fwd_bf16(const void* x, int64_t ld_x, const void* w, void* y, int6
 
 /* The same two entry points with an explicit kernel choice PER CALL (A/B timing, tests that compare two kernels on one shape;
  * there is no process-wide switch).  kernel_opts bit 0: the 3x3 stride-1 layers run in the generic tiled kernel instead of the
- * halo-patch kernels; bit 1: the tiled kernels store their output 8 bytes per lane instead of staging it for 16-byte stores;
+ * halo-patch kernels; bit 1: the tiled kernels store their output 8 bytes per lane instead of staging it for 16-byte stores (a store-width
+ * option: the same bits in y, dx - accumulated too - and the statistics; it is also what runs without the bit for Cout % 8 != 0, ld % 8 != 0
+ * or a destination that is not 16-byte aligned, in the tiled, ring and 8-wave kernels alike);
  * bit 2: a stride-2 input gradient runs as one launch per parity class (four) instead of one merged launch; bit 3: the 3x3
  * stride-1 layers run in the 8-wave lockstep halo-patch kernel (csrc/conv_patch.hip) instead of the loader / consumer ring
  * (csrc/conv_ring.hip, the default since round 4); bit 4: layers of the tiled kernel that fill the chip with 256 x 128 tiles run in
@@ -71,7 +73,8 @@ int ep24_conv_fwd_bf16(const void* x, int64_t ld_x, const void* w, void* y, int6
  * CU - the 20 x 20 level at B = 20 - run in 128-wide tiles with three LDS stages and two tiles in flight; with bit 7 they run in 64-wide
  * two-stage tiles as before; bit-identical results); bit 8: 1x1 stride-1 layers with 128 < K <= 256 and fewer than 100 000 pixels run
  * in the tiled kernel, as they did before the streaming kernel's weight tile was requested in one batch (round 5: the streaming kernel
- * is the default for every 1x1 stride-1 layer with K <= 256 now); bit 9: 3x3 stride-1 layers with at most 64 channels on either side
+ * is the default for every 1x1 stride-1 layer with K <= 256 now; y and a first-writer dx are bit-identical either way, an ACCUMULATED dx
+ * is not - the tiled kernel rounds twice, the streaming kernel once: see ep24_conv_dgrad_bf16); bit 9: 3x3 stride-1 layers with at most 64 channels on either side
  * run in the tiled kernel instead of conv_wreg_kernel (round 5, csrc/conv_wreg.hip: every weight fragment of the layer in registers,
  * persistent workgroups, one LDS window per tap row; bit-identical outputs, the batch statistics equal to fp32 summation order; the
  * default for such layers with at least 65 536 pixels, an image at least 32 wide and a plain first-writer destination).  kernel_opts = 0 is exactly ep24_conv_fwd_bf16 / ep24_conv_dgrad_bf16, and every default kernel of a 3x3 stride-1
@@ -115,7 +118,15 @@ int ep24_conv_kernel_for_ex(int dgrad, int B, int H, int W, int Cin, int Cout, i
                             int kernel_opts);
 
 /* dx[B,H,W,Cin] (+)= conv_transpose(dy[B,OH,OW,Cout_k], wt[Cin][k*k][Cout_k]); Cout_k % 8 == 0 (zero padded).
- * wt is the pure transpose of w (no tap flip).  Replaces autograd's conv input gradient. */
+ * wt is the pure transpose of w (no tap flip).  Replaces autograd's conv input gradient.
+ * accumulate = 0: dx = bf16(acc), acc the fp32 sum.  accumulate = 1, by the kernel that runs (ep24_conv_kernel_for(1, ...)):
+ *   - the streaming 1x1 kernel (id 2: 1x1 stride-1 with Cout_k <= 256; also ep24_conv1x1_dgrad_bnr_bf16 and
+ *     ep24_conv1x1_dgrad_bnbwd_bf16, which are forms of it): dx = bf16(acc + float(dx)) - ONE rounding;
+ *   - every other kernel (tiled - all stride-2 input gradients, merged or per parity class, and 1x1 layers under kernel_opts bit 8
+ *     -, ring, 8-wave halo patch; the weights-in-registers kernel does not accumulate, its layers run in the tiled kernel then):
+ *     dx = bf16(float(bf16(acc)) + float(dx)) - TWO roundings, through the 16-byte and the 8-byte store path alike (kernel_opts
+ *     bit 1, ld_dx % 8 != 0, Cin % 8 != 0 or a dx that is not 16-byte aligned select the path, never the value).
+ * tests/test_gpu_conv_exact.py holds every path to its form bit for bit. */
 int ep24_conv_dgrad_bf16(const void* dy, int64_t ld_dy, const void* wt, void* dx, int64_t ld_dx, int accumulate,
                          int B, int H, int W, int Cin, int Cout_k, int ksize, int stride, void* stream);
 
