@@ -2,6 +2,7 @@
 // area range "all", no crowd / ignore regions, one maxDets) with matching and accumulation on the GPU.
 //
 //   eval_iou      pairwise IoU matrix [G][D] (double) of GT rows against detections, for tests and for the host API
+//                 (circle24 and rect in 26 floats of geometry per object; poly24, the exact area IoU of poly24.h, in 48)
 //   eval_match    one workgroup per image: GT count / geometry into LDS, the image's detections sorted by (class, score desc,
 //                 p asc) in global scratch, then one wave per class segment greedily matches the first max_dets detections
 //                 against the class's GTs for all 10 IoU thresholds and appends one record per detection
@@ -12,6 +13,7 @@
 // append offset of a class segment's records (the sort key fixes the final order; (class, seq, rank) is unique).
 // No floating-point atomics anywhere.
 #include "geom.h"
+#include "poly24.h"
 
 namespace {
 
@@ -29,9 +31,12 @@ __device__ __forceinline__ uint32_t ord_desc(float s) {
 }
 
 // GT geometry from a label row's 50 coordinates (centre, 24 vertices): circle24 = (cx, cy, r[24]) with the expressions of
-// pairwise_kernel (loss.hip); rect = (x0, y0, x1, y1) = min / max over the vertices
+// pairwise_kernel (loss.hip); rect = (x0, y0, x1, y1) = min / max over the vertices; poly24 (GW = 48) = the 24 vertices
+template <int GW>
 __device__ __forceinline__ void gt_geometry(const float* t50, int iou_type, float* out) {
-    if (iou_type == 0) {
+    if constexpr (GW == 48) {
+        for (int k = 0; k < 48; ++k) out[k] = t50[2 + k];
+    } else if (iou_type == 0) {
         out[0] = t50[0];
         out[1] = t50[1];
         for (int k = 0; k < 24; ++k) {
@@ -50,9 +55,15 @@ __device__ __forceinline__ void gt_geometry(const float* t50, int iou_type, floa
 
 // Detection geometry from (cx, cy, r[24]): circle24 keeps it, rect = min / max over c + r_k * (cos, sin)(15 deg * k) with the
 // cos / sin table cs[48] the host computes in float64 and rounds.  NOT post_prepare's NMS rectangle, which keeps the reference's
-// theta * cos(theta) factors (boxes.py:31-33).
+// theta * cos(theta) factors (boxes.py:31-33).  poly24 (GW = 48) keeps the 24 points themselves, product and sum in fp32 as for rect.
+template <int GW>
 __device__ __forceinline__ void det_geometry(const float* q26, int iou_type, const float* cs, float* out) {
-    if (iou_type == 0) {
+    if constexpr (GW == 48) {
+        for (int k = 0; k < 24; ++k) {
+            out[2 * k] = q26[0] + q26[2 + k] * cs[k];
+            out[2 * k + 1] = q26[1] + q26[2 + k] * cs[24 + k];
+        }
+    } else if (iou_type == 0) {
         for (int k = 0; k < 26; ++k) out[k] = q26[k];
     } else {
         float x0 = INFINITY, y0 = INFINITY, x1 = -INFINITY, y1 = -INFINITY;
@@ -90,19 +101,24 @@ __device__ __forceinline__ double rect_iou(const float* g, const float* q) {
     return inter / (ag + ad - inter);
 }
 
+template <int GW>
 __device__ __forceinline__ double pair_iou(const float* g, const float* q, int iou_type) {
-    return iou_type == 0 ? (double)circle24_iou(g, q) : rect_iou(g, q);
+    if constexpr (GW == 48) return poly24_iou(g, q);
+    else return iou_type == 0 ? (double)circle24_iou(g, q) : rect_iou(g, q);
 }
 
+// GW = floats of geometry per object: 26 for circle24 / rect (the kernels as they were), 48 for poly24.  GS = the LDS row stride
+// of the match kernel: 49 for poly24, so that the 64 lanes' rows fall into different banks.
+template <int GW>
 __global__ __launch_bounds__(256) void eval_iou_kernel(const float* gt50, const float* det26, int G, int D, int iou_type,
                                                        const float* cs, double* out) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= (long)G * D) return;
     const int g = (int)(i / D), d = (int)(i - (long)g * D);
-    float gg[26], qq[26];
-    gt_geometry(gt50 + (long)g * 50, iou_type, gg);
-    det_geometry(det26 + (long)d * 26, iou_type, cs, qq);
-    out[i] = pair_iou(gg, qq, iou_type);
+    float gg[GW], qq[GW];
+    gt_geometry<GW>(gt50 + (long)g * 50, iou_type, gg);
+    det_geometry<GW>(det26 + (long)d * 26, iou_type, cs, qq);
+    out[i] = pair_iou<GW>(gg, qq, iou_type);
 }
 
 // Where detection r of image b lives: row = rows + (row_off[b] + a) * ncols with a = keep[b * keep_stride + r] (the NMS output of
@@ -136,12 +152,14 @@ __device__ __forceinline__ const float* det_row(const DetSrc& s, int b, int r, f
     return row;
 }
 
+template <int GW>
 __global__ __launch_bounds__(256) void eval_match_kernel(const float* labels, int L, DetSrc src, const int32_t* count, int C,
                                                          int iou_type, const float* cs, const double* thr, int max_dets,
                                                          int64_t seq_base, uint64_t* skey, int P, int64_t* rec_key,
                                                          int32_t* rec_cls, int32_t* rec_p, int32_t* rec_tp, int32_t* rec_count,
                                                          int32_t* npig, int32_t* err) {
-    __shared__ float g_geo[EV_MAX_L][26];
+    constexpr int GS = GW == 48 ? 49 : GW;
+    __shared__ float g_geo[EV_MAX_L][GS];
     __shared__ int g_cls[EV_MAX_L];
     __shared__ double thr_sh[EV_T];
     __shared__ float cs_sh[48];
@@ -165,7 +183,7 @@ __global__ __launch_bounds__(256) void eval_match_kernel(const float* labels, in
         const int c = (t[0] >= 0.f && t[0] < (float)C) ? (int)t[0] : -1;
         g_cls[i] = c;
         if (c >= 0) atomicAdd(&npig[c], 1);
-        gt_geometry(t + 1, iou_type, g_geo[i]);
+        gt_geometry<GW>(t + 1, iou_type, g_geo[i]);
     }
     const int nd = count[b];
     if (nd > P || nd < 0) {                               // host sizes P from the plan; never expected
@@ -244,11 +262,11 @@ __global__ __launch_bounds__(256) void eval_match_kernel(const float* labels, in
                     float sc;
                     int cc;
                     const float* row = det_row(src, b, p, sc, cc, C);
-                    float qg[26];
-                    det_geometry(row, iou_type, cs_sh, qg);
+                    float qg[GW];
+                    det_geometry<GW>(row, iou_type, cs_sh, qg);
                     double iou[4];
 #pragma unroll
-                    for (int q = 0; q < 4; ++q) iou[q] = has[q] ? pair_iou(g_geo[q * 64 + lane], qg, iou_type) : -1.0;
+                    for (int q = 0; q < 4; ++q) iou[q] = has[q] ? pair_iou<GW>(g_geo[q * 64 + lane], qg, iou_type) : -1.0;
                     for (int t = 0; t < EV_T; ++t) {
                         // pycocotools: the largest IoU >= min(t, 1 - 1e-10) among unmatched GTs, equal IoUs -> the later GT row
                         double best = thr_sh[t];
@@ -498,9 +516,12 @@ extern "C" int ep24_eval_iou(const float* gt50, const float* det26, int G, int D
                              void* stream) {
     if ((long)G * D == 0) return EP24_OK;
     EP24_REQUIRE(gt50 && det26 && ray_cs && out && G > 0 && D > 0, EP24_E_ARG, "eval_iou: bad arguments");
-    EP24_REQUIRE(iou_type == 0 || iou_type == 1, EP24_E_UNSUPPORTED, "eval_iou: iou_type %d (0 circle24, 1 rect)", iou_type);
-    hipLaunchKernelGGL(eval_iou_kernel, dim3((unsigned)(((long)G * D + 255) / 256)), dim3(256), 0, S_, gt50, det26, G, D, iou_type,
-                       ray_cs, out);
+    EP24_REQUIRE(iou_type >= 0 && iou_type <= 2, EP24_E_UNSUPPORTED, "eval_iou: iou_type %d (0 circle24, 1 rect, 2 poly24)", iou_type);
+    const dim3 grid((unsigned)(((long)G * D + 255) / 256));
+    if (iou_type == 2)
+        hipLaunchKernelGGL(eval_iou_kernel<48>, grid, dim3(256), 0, S_, gt50, det26, G, D, iou_type, ray_cs, out);
+    else
+        hipLaunchKernelGGL(eval_iou_kernel<26>, grid, dim3(256), 0, S_, gt50, det26, G, D, iou_type, ray_cs, out);
     EP24_LAUNCH_CHECK("ep24_eval_iou");
     return EP24_OK;
 }
@@ -522,10 +543,14 @@ extern "C" int ep24_eval_match(const float* labels, int L, int B, const float* r
     EP24_REQUIRE(P <= 65536 && (P & (P - 1)) == 0, EP24_E_UNSUPPORTED, "eval_match: P=%d (a power of two, at most 65536 detections per image)", P);
     EP24_REQUIRE(seq_base >= 0 && seq_base + B <= (1LL << 25), EP24_E_UNSUPPORTED, "eval_match: image sequence %lld + %d beyond 2^25",
                  (long long)seq_base, B);
-    EP24_REQUIRE(iou_type == 0 || iou_type == 1, EP24_E_UNSUPPORTED, "eval_match: iou_type %d (0 circle24, 1 rect)", iou_type);
+    EP24_REQUIRE(iou_type >= 0 && iou_type <= 2, EP24_E_UNSUPPORTED, "eval_match: iou_type %d (0 circle24, 1 rect, 2 poly24)", iou_type);
     DetSrc src{rows, ncols, row_off, keep, keep_stride, conf, cls};
-    hipLaunchKernelGGL(eval_match_kernel, dim3(B), dim3(256), 0, S_, labels, L, src, count, num_classes, iou_type, ray_cs, iou_thr,
-                       max_dets, seq_base, (uint64_t*)sort_scratch, P, rec_key, rec_cls, rec_p, rec_tp, rec_count, npig, err);
+    if (iou_type == 2)
+        hipLaunchKernelGGL(eval_match_kernel<48>, dim3(B), dim3(256), 0, S_, labels, L, src, count, num_classes, iou_type, ray_cs,
+                           iou_thr, max_dets, seq_base, (uint64_t*)sort_scratch, P, rec_key, rec_cls, rec_p, rec_tp, rec_count, npig, err);
+    else
+        hipLaunchKernelGGL(eval_match_kernel<26>, dim3(B), dim3(256), 0, S_, labels, L, src, count, num_classes, iou_type, ray_cs,
+                           iou_thr, max_dets, seq_base, (uint64_t*)sort_scratch, P, rec_key, rec_cls, rec_p, rec_tp, rec_count, npig, err);
     EP24_LAUNCH_CHECK("ep24_eval_match");
     return EP24_OK;
 }

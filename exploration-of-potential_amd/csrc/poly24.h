@@ -1,0 +1,83 @@
+// ep24 - exact area IoU of two 24-gons ("poly24", iou_type 2 of the evaluator).
+//
+// Signed trapezoid decomposition: with s_e = sign(x1 - x0) of an edge and h_e(x) its height above a common baseline, the
+// indicator of a simple polygon A above the baseline is -sigma_A * sum_e s_e [x in e][y < h_e(x)] (sigma = sign of the shoelace
+// area), so  |A and B| = sigma_A sigma_B * sum_e sum_f s_e s_f * integral over the common x range of min(h_e, h_f).
+// No inside tests, no sorting, continuous in the vertices: coincident edges, shared vertices and identical polygons are ordinary
+// cases.  Everything is double; the library is built with -ffp-contract=off, so every product and sum rounds on its own.
+#pragma once
+#include "common.h"
+
+// height of the edge (xa, ha) -> (xb, hb), xa < xb, at x
+__device__ __forceinline__ double poly24_height(double x, double xa, double ha, double xb, double hb) {
+    return ha + ((x - xa) * (hb - ha)) / (xb - xa);
+}
+
+// a, b: 24 vertices each as (x, y) pairs of fp32, promoted here.  Any NaN coordinate gives NaN (it never matches); vertex
+// boxes that do not overlap with positive width and height give exactly 0.0.
+__device__ inline double poly24_iou(const float* a, const float* b) {
+    double axl = INFINITY, axh = -INFINITY, ayl = INFINITY, ayh = -INFINITY;
+    double bxl = INFINITY, bxh = -INFINITY, byl = INFINITY, byh = -INFINITY;
+    bool nan = false;
+    for (int k = 0; k < 24; ++k) {
+        const double ax = a[2 * k], ay = a[2 * k + 1], bx = b[2 * k], by = b[2 * k + 1];
+        nan |= ax != ax || ay != ay || bx != bx || by != by;
+        axl = fmin(axl, ax); axh = fmax(axh, ax); ayl = fmin(ayl, ay); ayh = fmax(ayh, ay);
+        bxl = fmin(bxl, bx); bxh = fmax(bxh, bx); byl = fmin(byl, by); byh = fmax(byh, by);
+    }
+    if (nan) return __builtin_nan("");
+    if (!(fmin(axh, bxh) - fmax(axl, bxl) > 0.0 && fmin(ayh, byh) - fmax(ayl, byl) > 0.0)) return 0.0;
+    // the shoelace areas and the heights are taken relative to (xb, yb), the low corner of the joint box: a translation, exact in
+    // real arithmetic, that keeps the rounding relative to the objects' size and not to their position in the image
+    const double xb = fmin(axl, bxl), yb = fmin(ayl, byl);
+    double sa = 0.0, sb = 0.0;
+    for (int k = 0; k < 24; ++k) {
+        const int k1 = k == 23 ? 0 : k + 1;
+        const double ax0 = (double)a[2 * k] - xb, ay0 = (double)a[2 * k + 1] - yb;
+        const double ax1 = (double)a[2 * k1] - xb, ay1 = (double)a[2 * k1 + 1] - yb;
+        sa += ax0 * ay1 - ax1 * ay0;
+        const double bx0 = (double)b[2 * k] - xb, by0 = (double)b[2 * k + 1] - yb;
+        const double bx1 = (double)b[2 * k1] - xb, by1 = (double)b[2 * k1 + 1] - yb;
+        sb += bx0 * by1 - bx1 * by0;
+    }
+    sa *= 0.5;
+    sb *= 0.5;
+    double S = 0.0;
+    for (int i = 0; i < 24; ++i) {
+        const int i1 = i == 23 ? 0 : i + 1;
+        const double ex0 = a[2 * i], ex1 = a[2 * i1];
+        if (ex0 == ex1) continue;
+        const double eh0 = (double)a[2 * i + 1] - yb, eh1 = (double)a[2 * i1 + 1] - yb;
+        const bool er = ex1 > ex0;                            // left to right as stored
+        const double exa = er ? ex0 : ex1, eha = er ? eh0 : eh1, exb = er ? ex1 : ex0, ehb = er ? eh1 : eh0;
+        for (int j = 0; j < 24; ++j) {
+            const int j1 = j == 23 ? 0 : j + 1;
+            const double fx0 = b[2 * j], fx1 = b[2 * j1];
+            if (fx0 == fx1) continue;
+            const double fh0 = (double)b[2 * j + 1] - yb, fh1 = (double)b[2 * j1 + 1] - yb;
+            const bool fr = fx1 > fx0;
+            const double fxa = fr ? fx0 : fx1, fha = fr ? fh0 : fh1, fxb = fr ? fx1 : fx0, fhb = fr ? fh1 : fh0;
+            const double xl = fmax(exa, fxa), xr = fmin(exb, fxb);
+            if (!(xl < xr)) continue;
+            const double al = poly24_height(xl, exa, eha, exb, ehb), ar = poly24_height(xr, exa, eha, exb, ehb);
+            const double bl = poly24_height(xl, fxa, fha, fxb, fhb), br = poly24_height(xr, fxa, fha, fxb, fhb);
+            const double dl = al - bl, dr = ar - br;
+            const double ml = fmin(al, bl), mr = fmin(ar, br);
+            double term;
+            if ((dl < 0.0 && dr > 0.0) || (dl > 0.0 && dr < 0.0)) {
+                // the edges cross inside the range: two trapezoids under min(e, f) that meet at the crossing height
+                const double t = dl / (dl - dr);
+                const double xm = xl + t * (xr - xl), hm = al + t * (ar - al);
+                term = 0.5 * (ml + hm) * (xm - xl) + 0.5 * (hm + mr) * (xr - xm);
+            } else {
+                term = 0.5 * (ml + mr) * (xr - xl);
+            }
+            S += (er == fr) ? term : -term;
+        }
+    }
+    const double aa = fabs(sa), ab = fabs(sb);
+    const double sg = ((sa < 0.0) != (sb < 0.0)) ? -S : S;
+    const double inter = fmin(fmax(sg, 0.0), fmin(aa, ab));
+    const double uni = aa + ab - inter;
+    return uni > 0.0 ? inter / uni : 0.0;
+}

@@ -3,11 +3,13 @@
 The reference scores axis-aligned boxes through pycocotools and never wires an evaluator into its 24-point trainer
 (exp/yolox_base.py ``get_evaluator`` is commented out).  ``Evaluator24`` gives the trainer a validation metric with the
 semantics of pycocotools ``evaluateImg`` + ``accumulate`` for one area range ("all"), no crowd / ignore regions and one
-``maxDets``, over two IoU types:
+``maxDets``, over three IoU types:
 
 * ``"circle24"`` (default): the model's own geometry - per ray the IoU of the GT's and the detection's ray circles
   (``ray_inter`` of geom.h), averaged over the 24 rays in fp32.  A similarity in [0, 1], not the loss's GIoU.
 * ``"rect"``: the bounding boxes of the 24 points (detections: c + r_k (cos, sin)(15 deg k)), IoU in float64.
+* ``"poly24"``: the exact area IoU of the two 24-gons (GT vertices against the detection's 24 points) in float64
+  (csrc/poly24.h): how well the predicted shape covers the object.
 
 Matching (per image and class, all 10 thresholds), the sort of the records over the whole evaluation and the accumulation
 run as HIP kernels; the host reads one count per batch and, in ``summarize``, the [10, 101, C] precision and [10, C] recall
@@ -19,7 +21,7 @@ import torch
 from . import _lib
 from ._lib import Ep24Error, call, ptr, stream_ptr
 
-IOU_TYPES = {"circle24": 0, "rect": 1}
+IOU_TYPES = {"circle24": 0, "rect": 1, "poly24": 2}
 IOU_THRS = np.linspace(0.5, 0.95, 10)                    # float64, as pycocotools Params
 REC_THRS = np.linspace(0.0, 1.0, 101)
 MAX_GT_ROWS = 256

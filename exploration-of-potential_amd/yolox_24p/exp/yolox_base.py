@@ -55,7 +55,7 @@ class Exp(BaseExp):
         self.nmsthre = 0.65
         self.eval_len = 64               # images of the synthetic validation set (get_eval_loader)
         self.eval_seed = 1               # its own seed: the training source uses 0
-        self.eval_iou_type = "circle24"  # ep24.evaluate: "circle24" (the model's geometry) or "rect" (bounding boxes)
+        self.eval_iou_type = "circle24"  # ep24.evaluate: "circle24" (the model's geometry), "rect" (bounding boxes) or "poly24" (polygon area)
 
     def get_model(self):
         from models import YOLOX, YOLOPAFPN, YOLOXHead

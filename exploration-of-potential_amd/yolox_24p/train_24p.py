@@ -396,12 +396,16 @@ def make_parser():
     p.add_argument("--augment-seed", default=0, type=int, help="seed of the augmentation; a batch's parameters follow from (seed, epoch, iteration)")
     p.add_argument("--eval-interval", default=0, type=int, help="every N epochs: COCO-style AP (exp.eval, ep24.evaluate) of the EMA model "
                    "(--ema) or the model, logged and saved as best_ckpt.pth when it improves (0 = off; single process only)")
+    p.add_argument("--eval-iou", default=None, choices=["circle24", "rect", "poly24"], help="IoU type of the evaluation (ep24.evaluate): "
+                   "overrides the Exp's eval_iou_type; poly24 is the exact area IoU of the 24-point polygons")
     return p
 
 
 def main(exp, args):
     if args.output_dir:
         exp.output_dir = args.output_dir
+    if getattr(args, "eval_iou", None) is not None:
+        exp.eval_iou_type = args.eval_iou
     if args.synthetic_len:
         exp.synthetic_len = args.synthetic_len
     trainer = Trainer(exp, args)

@@ -544,7 +544,9 @@ int ep24_post_gather(const float* pred, int ncols, const float* conf, const int3
 /* ------------------------------------------------------------------------------------------------
  * E1  evaluation: COCO-style AP of 24-point detections (pycocotools evaluateImg + accumulate, area "all", no crowd /
  *     ignore, one maxDets; csrc/evaluate.hip).  iou_type 0 = circle24 (mean over the 24 rays of the ray circles' IoU,
- *     fp32), 1 = rect (axis-aligned boxes, float64).  ray_cs[48] = cos(15 deg * k), then sin(15 deg * k), fp32.
+ *     fp32), 1 = rect (axis-aligned boxes, float64), 2 = poly24 (exact area IoU of the two 24-gons, float64: GT vertices
+ *     against c + r_k * (cos, sin)(15 deg * k) formed in fp32; csrc/poly24.h).  ray_cs[48] = cos(15 deg * k), then
+ *     sin(15 deg * k), fp32.
  * ------------------------------------------------------------------------------------------------ */
 /* out[G][D] double = IoU of gt50[G][50] (centre + 24 vertices, label columns 1..50) against det26[D][26] (centre + 24 radii). */
 int ep24_eval_iou(const float* gt50, const float* det26, int G, int D, int iou_type, const float* ray_cs, double* out,
@@ -573,6 +575,30 @@ int ep24_eval_sort(const int64_t* key, const int32_t* cls, int64_t n, int key_lo
 int ep24_eval_accumulate(const int32_t* order, const int32_t* rec_cls, const int32_t* rec_tp, int64_t n, const int32_t* npig,
                          int num_classes, const double* rec_thr, int64_t* cls_range, int32_t* ctp_scratch,
                          double* env_scratch, double* precision, double* recall, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * E2  instance masks of 24-point polygons (csrc/mask.hip).  As everywhere in this header: raw device
+ *     pointers, sizes and a stream; the caller owns every buffer, nothing allocates, frees or synchronises.
+ *     Packed masks are uint32 [N][H][WW], WW = ceil(W / 32): pixel x is bit x & 31 of word x >> 5, bits at x >= W are zero.
+ *     bbox [N][4] int32 = (x0, y0, x1, y1), the smallest and largest set pixel, or (W, H, -1, -1) for an empty mask;
+ *     area [N] int32 = the number of set pixels.  H * W < 2^31.
+ * ------------------------------------------------------------------------------------------------ */
+/* verts[n][24][2] fp32 from rows det[n][ncols] = (cx, cy, 24 radii, ...): x_k = cx / ratio + (r_k / ratio) * ray_cs[k],
+ * y_k = cy / ratio + (r_k / ratio) * ray_cs[24 + k], every operation a separate fp32 one (ratio = 1 leaves the rows as they are;
+ * the letterbox ratio maps them back to the original image). */
+int ep24_poly24_vertices(const float* det, int ncols, int n, const float* ray_cs, float ratio, float* verts, void* stream);
+/* Rasterise verts[N][24][2] (already in the pixel coordinates of the H x W canvas).  The centre of pixel (x, y) is the point
+ * (x, y).  In double, for row yc = y the edge (x0, y0) -> (x1, y1) counts iff (y0 <= yc) != (y1 <= yc), crosses at
+ * xc = x0 + ((yc - y0) * (x1 - x0)) / (y1 - y0), and pixel x is set iff an odd number of counting edges have x < xc.  Every word
+ * of bits, bbox and area is written by the call itself (no memset needed); the statistics use integer atomics only. */
+int ep24_poly24_raster(const float* verts, int N, int H, int W, uint32_t* bits, int32_t* bbox, int32_t* area, void* stream);
+/* masks uint8 [N][H][W] (non-zero = set) -> packed bits with bbox and area, and back (0 / 1). */
+int ep24_mask_pack_u8(const uint8_t* masks, int N, int H, int W, uint32_t* bits, int32_t* bbox, int32_t* area, void* stream);
+int ep24_mask_unpack_u8(const uint32_t* bits, int N, int H, int W, uint8_t* masks, void* stream);
+/* inter[G][D] int64 = popcount(A_g & B_d) over the rows and words of the two boxes' overlap (a pair with disjoint boxes reads
+ * no mask word); iou[G][D] double = inter / (a_area + b_area - inter), 0 when that union is 0.  Integer sums only. */
+int ep24_mask_iou(const uint32_t* a_bits, const int32_t* a_bbox, const int32_t* a_area, int G, const uint32_t* b_bits,
+                  const int32_t* b_bbox, const int32_t* b_area, int D, int H, int W, int64_t* inter, double* iou, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * N4  24-point label generation (yolox_24p/datasets/2+24_labels_create.py:61-116, :175-180)
