@@ -59,10 +59,7 @@ __device__ __forceinline__ void gt_geometry(const float* t50, int iou_type, floa
 template <int GW>
 __device__ __forceinline__ void det_geometry(const float* q26, int iou_type, const float* cs, float* out) {
     if constexpr (GW == 48) {
-        for (int k = 0; k < 24; ++k) {
-            out[2 * k] = q26[0] + q26[2 + k] * cs[k];
-            out[2 * k + 1] = q26[1] + q26[2 + k] * cs[24 + k];
-        }
+        poly24_det_vertices(q26, cs, out);
     } else if (iou_type == 0) {
         for (int k = 0; k < 26; ++k) out[k] = q26[k];
     } else {

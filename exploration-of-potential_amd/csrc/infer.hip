@@ -2,6 +2,7 @@
 // (yolo_head_24p.py:190-210, 239-256) and `postprocess` (utils/boxes.py:29-99: class max, confidence filter,
 // bounding rectangle of the 24 points, per-class NMS).  Elementwise / latency kernels, no MFMA.
 #include "common.h"
+#include "nms_sort.h"
 
 namespace {
 
@@ -132,7 +133,7 @@ __global__ __launch_bounds__(256) void post_prepare_kernel(const float* pred, in
     }
 }
 
-// One workgroup per image: compact the candidates, bitonic-sort them by (score desc, index asc) in global scratch,
+// One workgroup per image: compact the candidates, bitonic-sort them by (score desc, index asc) in global scratch (nms_sort.h),
 // then greedy NMS (torchvision semantics: suppress IoU > thr, same class only unless class-agnostic).
 __global__ __launch_bounds__(1024) void nms_kernel(const float* score, const int* cls, const float* rect, int A, float thr,
                                                    int agnostic, float* skey, int* sidx, unsigned char* dead, int* keep,
@@ -147,30 +148,7 @@ __global__ __launch_bounds__(1024) void nms_kernel(const float* score, const int
     int* idx = sidx + (long)b * P;
     unsigned char* dd = dead + (long)b * P;
     int* kp = keep + (long)b * A;
-    if (tid == 0) n_sh = 0;
-    __syncthreads();
-    for (int a = tid; a < A; a += 1024)
-        if (sc[a] >= 0.f) { const int j = atomicAdd(&n_sh, 1); key[j] = sc[a]; idx[j] = a; }
-    __syncthreads();
-    const int n = n_sh;
-    int P2 = 1;
-    while (P2 < n) P2 <<= 1;
-    for (int j = n + tid; j < P2; j += 1024) { key[j] = -2.0f; idx[j] = 0x7FFFFFFF; }
-    __syncthreads();
-    for (int k = 2; k <= P2; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = tid; i < P2; i += 1024) {
-                const int l = i ^ j;
-                if (l > i) {
-                    const bool up = (i & k) == 0;          // "up" blocks hold the better (earlier) elements first
-                    const float ki = key[i], kl = key[l];
-                    const int ii = idx[i], il = idx[l];
-                    const bool i_first = ki > kl || (ki == kl && ii < il);
-                    if (up != i_first) { key[i] = kl; key[l] = ki; idx[i] = il; idx[l] = ii; }
-                }
-            }
-            __syncthreads();
-        }
+    const int n = nms_compact_sort<1024>(sc, A, key, idx, &n_sh);
     for (int j = tid; j < n; j += 1024) dd[j] = 0;
     __syncthreads();
     int kept = 0;

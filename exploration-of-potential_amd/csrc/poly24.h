@@ -8,6 +8,16 @@
 #pragma once
 #include "common.h"
 
+// The 24 points of a detection (cx, cy, r[24]) as (x, y) pairs: c + r_k * (cos, sin)(15 deg * k) with the table cs[48] the host
+// computes in float64 and rounds; product and sum are separate fp32 operations.  The one place the evaluator (det_geometry<48>)
+// and the polygon NMS form them.
+__device__ __forceinline__ void poly24_det_vertices(const float* q26, const float* cs, float* out) {
+    for (int k = 0; k < 24; ++k) {
+        out[2 * k] = q26[0] + q26[2 + k] * cs[k];
+        out[2 * k + 1] = q26[1] + q26[2 + k] * cs[24 + k];
+    }
+}
+
 // height of the edge (xa, ha) -> (xb, hb), xa < xb, at x
 __device__ __forceinline__ double poly24_height(double x, double xa, double ha, double xb, double hb) {
     return ha + ((x - xa) * (hb - ha)) / (xb - xa);

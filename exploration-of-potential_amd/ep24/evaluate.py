@@ -101,14 +101,20 @@ def _pow2(n):
 
 
 class Evaluator24:
-    """``Evaluator24(num_classes, iou_type="circle24", max_dets=100, conf_thre=0.01, nms_thre=0.65)``.
+    """``Evaluator24(num_classes, iou_type="circle24", max_dets=100, conf_thre=0.01, nms_thre=0.65, nms_iou="rect",
+    max_candidates=None)``.  ``nms_iou`` / ``max_candidates`` are ``ep24.infer.postprocess``'s: ``"poly24"`` lets ``update``
+    suppress by the polygons' area IoU (class-aware, as its rectangle NMS is).
 
     ``update(predictions, labels)``: decoded eval-mode predictions [B, A, 27 + C] (the evaluator runs post_prepare +
     post_nms itself) and the label table [B, L, 51]; ``update_detections(dets, labels)``: ``ep24.infer.postprocess`` output.
     Both give bit-identical results for the same detections.  ``summarize()`` returns a dict with ``AP`` (0.5:0.95),
     ``AP50``, ``AP75``, ``AR100``, ``per_class_AP`` and the tables; ``summary`` holds the printed form."""
 
-    def __init__(self, num_classes, iou_type="circle24", max_dets=100, conf_thre=0.01, nms_thre=0.65, device=None):
+    def __init__(self, num_classes, iou_type="circle24", max_dets=100, conf_thre=0.01, nms_thre=0.65, device=None, nms_iou="rect",
+                 max_candidates=None):
+        from .infer import check_nms_iou
+        check_nms_iou(nms_iou, max_candidates)
+        self.nms_iou, self.max_candidates = nms_iou, max_candidates
         if not 0 < int(num_classes) < 0xFFFF:
             raise Ep24Error("ep24: Evaluator24 takes 1 .. 65534 classes, got %d (EP24_E_UNSUPPORTED)" % num_classes)
         if not 0 < int(max_dets) <= MAX_DETS:
@@ -168,8 +174,11 @@ class Evaluator24:
         s = stream_ptr()
         call("post_prepare", ptr(pred), ncols, C, B * A, self.conf_thre, ptr(ws.ray), ptr(ws.score), ptr(ws.conf), ptr(ws.cls),
              ptr(ws.rect), s)
-        call("post_nms", ptr(ws.score), ptr(ws.cls), ptr(ws.rect), B, A, self.nms_thre, 0, ptr(ws.skey), ptr(ws.sidx), ptr(ws.dead),
-             ptr(ws.keep), ptr(ws.count), ws.P, s)
+        if self.nms_iou == "poly24":
+            infer.nms_poly24(ws, pred, ncols, B, A, self.nms_thre, False, self.max_candidates, s)
+        else:
+            call("post_nms", ptr(ws.score), ptr(ws.cls), ptr(ws.rect), B, A, self.nms_thre, 0, ptr(ws.skey), ptr(ws.sidx), ptr(ws.dead),
+                 ptr(ws.keep), ptr(ws.count), ws.P, s)
         rk = (B, A, str(pred.device))
         row_off = _row_offs.get(rk)
         if row_off is None:
@@ -293,6 +302,7 @@ class Evaluator24:
         precision, recall = self.accumulate()
         self.stats = summarize_tables(precision, recall)
         self.stats["iou_type"] = self.iou_type
+        self.stats["nms_iou"] = self.nms_iou
         self.stats["images"] = self.seq
         self.summary = format_summary(self.stats, self.max_dets)
         return self.stats

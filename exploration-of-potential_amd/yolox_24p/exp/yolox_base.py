@@ -56,6 +56,7 @@ class Exp(BaseExp):
         self.eval_len = 64               # images of the synthetic validation set (get_eval_loader)
         self.eval_seed = 1               # its own seed: the training source uses 0
         self.eval_iou_type = "circle24"  # ep24.evaluate: "circle24" (the model's geometry), "rect" (bounding boxes) or "poly24" (polygon area)
+        self.nms_iou_type = "rect"       # NMS of the evaluation: "rect" (the reference's rectangle rule) or "poly24" (the polygons' area IoU)
 
     def get_model(self):
         from models import YOLOX, YOLOPAFPN, YOLOXHead
@@ -146,7 +147,8 @@ class Exp(BaseExp):
         from ep24.evaluate import Evaluator24
         if is_distributed:
             raise Ep24Error("ep24: distributed evaluation (gathering records across ranks) is not implemented")
-        evaluator = Evaluator24(self.num_classes, iou_type=self.eval_iou_type, conf_thre=self.test_conf, nms_thre=self.nmsthre)
+        evaluator = Evaluator24(self.num_classes, iou_type=self.eval_iou_type, conf_thre=self.test_conf, nms_thre=self.nmsthre,
+                                nms_iou=self.nms_iou_type)
         evaluator.dataloader = self.get_eval_loader(batch_size)
         return evaluator
 

@@ -398,6 +398,8 @@ def make_parser():
                    "(--ema) or the model, logged and saved as best_ckpt.pth when it improves (0 = off; single process only)")
     p.add_argument("--eval-iou", default=None, choices=["circle24", "rect", "poly24"], help="IoU type of the evaluation (ep24.evaluate): "
                    "overrides the Exp's eval_iou_type; poly24 is the exact area IoU of the 24-point polygons")
+    p.add_argument("--nms-iou", default=None, choices=["rect", "poly24"], help="NMS of the evaluation: overrides the Exp's nms_iou_type; "
+                   "rect is the reference's rectangle rule, poly24 suppresses by the exact area IoU of the 24-point polygons")
     return p
 
 
@@ -406,6 +408,8 @@ def main(exp, args):
         exp.output_dir = args.output_dir
     if getattr(args, "eval_iou", None) is not None:
         exp.eval_iou_type = args.eval_iou
+    if getattr(args, "nms_iou", None) is not None:
+        exp.nms_iou_type = args.nms_iou
     if args.synthetic_len:
         exp.synthetic_len = args.synthetic_len
     trainer = Trainer(exp, args)

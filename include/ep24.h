@@ -540,6 +540,26 @@ int ep24_post_nms(const float* score, const int32_t* cls, const float* rect, int
                   int32_t* keep_count, int P, void* stream);
 int ep24_post_gather(const float* pred, int ncols, const float* conf, const int32_t* cls, const int32_t* keep, int n,
                      float* det, void* stream);
+/* Polygon NMS (csrc/polynms.hip): ep24_post_nms with the rectangle IoU replaced by the exact area IoU of
+ * the detections' own 24 points.  pred[B][A][ncols], score[B][A] and cls[B][A] are ep24_post_prepare's input and outputs.
+ *   Candidates and order are ep24_post_nms's: the rows with score >= 0 (obj * class_conf >= conf_thre), score descending, ties to
+ *   the lower row index; only the K best of an image enter (1 <= K <= A; K = A is exact greedy NMS over every candidate, a smaller
+ *   K drops the others: the usual nms_pre).  Candidate j is removed by a kept, better-placed candidate i iff the classes agree
+ *   (or class_agnostic) and poly24_iou(a = P_i, b = P_j) > (double)nms_thre, with P's vertices x_k = cx + r_k * ray_cs[k],
+ *   y_k = cy + r_k * ray_cs[24 + k] (product and sum separate fp32 operations, as ep24_eval_iou forms a detection's) and
+ *   poly24_iou the function of csrc/poly24.h that ep24_eval_iou calls (iou_type 2), one lane per pair: the same bits.  A NaN IoU
+ *   never suppresses: a row with a NaN coordinate is kept and removes nobody.  Pairs whose vertex boxes do not overlap have IoU
+ *   exactly 0.0, so they are never evaluated; that is exact for nms_thre >= 0, and a negative (or NaN) nms_thre is EP24_E_ARG.
+ *   Four launches, no host synchronisation: sort (sort_key / sort_idx [B][P], P a power of two >= A; n_cand[B] = min(candidates,
+ *   K)), geometry of the sorted candidates (verts [B][K][48], vbox [B][K][4] = min / max of the vertices, vcls [B][K]), the
+ *   suppression matrix mask [B][K][ceil(K / 64)] uint64 (bit j & 63 of word j >> 6 of row i set iff j > i, j < n_cand, class rule,
+ *   IoU test; every word the scan reads - rows < n_cand, words from the row's diagonal word to ceil(n_cand / 64) - 1 - is written
+ *   by the call, whatever the buffers held) and the scan (one workgroup per image).  keep [B][A] / keep_count [B] as ep24_post_nms
+ *   writes them.  EP24_E_ARG for a null pointer, K < 1, K > A or a bad P; EP24_E_UNSUPPORTED for K > 65536. */
+int ep24_post_nms_poly24(const float* pred, int ncols, const float* score, const int32_t* cls, int B, int A, int K,
+                         float nms_thre, int class_agnostic, const float* ray_cs, float* sort_key, int32_t* sort_idx, int P,
+                         int32_t* n_cand, float* verts, float* vbox, int32_t* vcls, uint64_t* mask, int32_t* keep,
+                         int32_t* keep_count, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * E1  evaluation: COCO-style AP of 24-point detections (pycocotools evaluateImg + accumulate, area "all", no crowd /
