@@ -3,7 +3,8 @@
 Host side (this file) computes what is 1-D and cheap exactly as the reference does with numpy - the angle / radius
 tables, the target row count T from the arc length, the crop box - and caches, per (Theta, T), the device-resident
 winner map built by ``ep24_sector_map``.  Per image only ``ep24_resize_linear_u8`` + ``ep24_sector_gather`` (+
-``ep24_mask_bbox``) run.  Inputs may be numpy HWC uint8 arrays (drop-in: results come back as numpy) or CUDA tensors.
+``ep24_mask_bbox``) run.  ``geometry`` / ``map_points`` are the continuous form of the same map, for points instead of pixels
+(``ep24.fisheye`` warps the 24-point labels with it).  Inputs may be numpy HWC uint8 arrays (drop-in: results come back as numpy) or CUDA tensors.
 """
 import numpy as np
 import torch
@@ -50,6 +51,18 @@ def _crop_box(canvas_w, c, s, rho):
     return dest_y(vy_max), dest_y(vy_min), dest_x(vx_min), dest_x(vx_max)       # y0, y1, x0, x1
 
 
+_GEOMETRY = {}
+
+
+def _geometry(theta_deg, h, w, custom_rows=None):
+    key = (float(theta_deg), int(h), int(w), None if custom_rows is None else int(custom_rows))
+    if key not in _GEOMETRY:
+        canvas_w, c, s, rho, T = _tables(theta_deg, h, w, custom_rows)
+        y0, y1, x0, x1 = _crop_box(canvas_w, c, s, rho)
+        _GEOMETRY[key] = (T, canvas_w, (y0, y1, x0, x1), (y1 - y0, x1 - x0))
+    return _GEOMETRY[key]
+
+
 class Image_Distortion:
     def __init__(self, device="cuda:0"):
         self.draw_temp_size = CANVAS
@@ -70,6 +83,24 @@ class Image_Distortion:
             torch.cuda.current_stream().synchronize()        # ct/st/rt may be freed after this point (one-time build)
             self._maps[key] = (winner, canvas_w, _crop_box(canvas_w, c, s, rho), T)
         return self._maps[key]
+
+    @staticmethod
+    def geometry(theta, h, w, custom_rows=None):
+        """(T, canvas width, crop box (y0, y1, x0, x1), warped size (h', w')) of an h x w image at angle ``theta``: host only, from
+        the 1-D tables, cached per argument tuple.  No winner map is built."""
+        return _geometry(theta, h, w, custom_rows)
+
+    def map_points(self, points, theta, h, w, custom_rows=None):
+        """points [m,2] (x, y) in pixel-index coordinates of the h x w source image (pixel i is centred at i) -> their positions
+        [m,2] float64 in the warped image, on the device, through the continuous sector map (``ep24_sector_points``)."""
+        _lib.require_gpu()
+        pts = torch.as_tensor(points, dtype=torch.float64).to(self.device).contiguous()
+        if pts.dim() != 2 or pts.shape[1] != 2:
+            raise IndexError("map_points takes points [m,2]")
+        T, cw, (y0, _, x0, _), _ = _geometry(theta, h, w, custom_rows)
+        out = torch.empty_like(pts)
+        call("sector_points", ptr(pts), pts.shape[0], float(theta), T, int(h), int(w), cw, x0, y0, ptr(out), stream_ptr())
+        return out
 
     def source_index(self, theta_deg, h, w, custom_rows=None):
         """[out_h, out_w] int32 flat index into the resized image (-1 = fill): the scatter's winners."""

@@ -70,6 +70,8 @@ class Trainer:
         args.raw_u8 = not (args.fp32_batches or args.no_prefetch)
         if args.augment and not args.raw_u8:
             raise SystemExit("train_24p.py: --augment works on the raw uint8 batches behind the prefetcher (drop --no-prefetch / --fp32-batches)")
+        if args.fisheye_theta is not None:
+            check_fisheye_args(args)
         self.train_loader = exp.get_data_loader(args.batch_size, raw_u8=bool(args.raw_u8), workers=args.loader_workers,
                                                  pin=None if args.loader_pin is None else bool(args.loader_pin))
         self.loss_func = Loss_Function(exp.num_classes)
@@ -292,6 +294,8 @@ class Trainer:
         from ep24.input import DataPrefetcher, TrainTransform
         if self.args.augment:
             pf = DataPrefetcher(self.positioned(self.train_loader), tuple(self.input_size), self.augment_transform())
+        elif self.args.fisheye_theta is not None:
+            pf = DataPrefetcher(self.positioned(self.train_loader), tuple(self.input_size), self.fisheye_transform())
         else:
             pf = DataPrefetcher(self.train_loader, tuple(self.input_size), TrainTransform(max_labels=50))
         self.prefetcher = pf                              # its t_loader / t_upload split the throughput record's host time
@@ -314,6 +318,14 @@ class Trainer:
             from datasets import MosaicTransform
             self.transform = MosaicTransform.from_exp(self.exp, max_labels=50, seed=self.args.augment_seed)
         self.transform.enabled = self.epoch < self.max_epoch - self.exp.no_aug_epochs
+        return self.transform
+
+    def fisheye_transform(self):
+        """--fisheye-theta LO HI: ONE ``FisheyeTransform`` for the run - every image through the sector warp at an angle drawn per
+        image, its 24-point labels through the same warp (ep24.fisheye)."""
+        if getattr(self, "transform", None) is None:
+            from ep24.fisheye import FisheyeTransform
+            self.transform = FisheyeTransform(theta=tuple(self.args.fisheye_theta), max_labels=50, seed=self.args.augment_seed)
         return self.transform
 
     def positioned(self, loader):
@@ -352,6 +364,17 @@ class Trainer:
         if self.ema_model is not None:
             state["ema_model"], state["ema_updates"] = self.ema_model.ema.state_dict(), self.ema_model.updates
         save_checkpoint(state, update_best_ckpt, self.file_name, ckpt_name)
+
+
+def check_fisheye_args(args):
+    """--fisheye-theta works on the raw uint8 batches, and the warp is not composed with mosaic / affine."""
+    lo, hi = args.fisheye_theta
+    if args.augment:
+        raise SystemExit("train_24p.py: --fisheye-theta and --augment exclude each other (the sector warp is not composed with mosaic / affine)")
+    if not args.raw_u8:
+        raise SystemExit("train_24p.py: --fisheye-theta works on the raw uint8 batches behind the prefetcher (drop --no-prefetch / --fp32-batches)")
+    if not 15 <= lo <= hi <= 180:
+        raise SystemExit("train_24p.py: --fisheye-theta LO HI needs 15 <= LO <= HI <= 180")
 
 
 def make_parser():
@@ -394,6 +417,9 @@ def make_parser():
                    "MosaicTransform behind the prefetcher) with the Exp's mosaic_prob / degrees / translate / mosaic_scale / shear / flip_prob / "
                    "hsv_prob, for epochs < max_epoch - no_aug_epochs")
     p.add_argument("--augment-seed", default=0, type=int, help="seed of the augmentation; a batch's parameters follow from (seed, epoch, iteration)")
+    p.add_argument("--fisheye-theta", default=None, type=int, nargs=2, metavar=("LO", "HI"), help="fisheye sector warp of every image AND its "
+                   "24-point labels on the GPU (ep24.fisheye.FisheyeTransform behind the prefetcher), one angle in [LO, HI] degrees per image, "
+                   "reproducible from (--augment-seed, epoch, iteration); not together with --augment")
     p.add_argument("--eval-interval", default=0, type=int, help="every N epochs: COCO-style AP (exp.eval, ep24.evaluate) of the EMA model "
                    "(--ema) or the model, logged and saved as best_ckpt.pth when it improves (0 = off; single process only)")
     p.add_argument("--eval-iou", default=None, choices=["circle24", "rect", "poly24"], help="IoU type of the evaluation (ep24.evaluate): "

@@ -504,6 +504,34 @@ int ep24_resize_linear_u8(const uint8_t* src, int sh, int sw, uint8_t* dst, int 
 int ep24_sector_warp_u8(const uint8_t* src, int sh, int sw, const int32_t* winner, int canvas_w, int y0, int x0,
                         int out_h, int out_w, int T, int n_ang, uint8_t* dst, int fill, void* stream);
 
+/* The continuous sector map: the scatter above with its truncations removed.  For an image h x w, angle Theta,
+ * row count T, canvas width cw, crop origin (x0, y0) and N = 13200, a source point (u, v) in pixel-index coordinates (pixel i is
+ * centred at i; u = x_norm * w, v = y_norm * h) goes to, all in double,
+ *     dx = (u + 0.5) * (N / w) - 0.5               dy = (v + 0.5) * (T / h) - 0.5
+ *     a  = (N - 1) - dx                            r  = (T - 1) - dy
+ *     th = ((180 - Theta) / 2 + Theta * a / (N - 1)) * pi / 180
+ *     rho = (1000 - T) + T * r / (T - 1)           c = rho * cos th,  s = rho * sin th
+ *     X = c + cw / 2 - 1 - x0 - 0.5 * sign(c)      Y = 1000 - s - 1 - y0 + 0.5
+ * The +-0.5 terms put the point at the centre of the pixel that the truncation toward zero selects.
+ * points [m][2] and out [m][2] are device float64 (x, y); one thread per point; m == 0 is EP24_OK. */
+int ep24_sector_points(const double* points, int m, double theta, int T, int h, int w, int canvas_w, int x0, int y0, double* out,
+                       void* stream);
+/* 24-point labels under the warp, two launches, no allocation, no synchronisation, no floating-point atomics.
+ * rows [R][51] float64: the normalised label rows (class, cx, cy, 24 x (x, y)) of all images, concatenated.
+ * geo [n][12] float64 per image: Theta, T, h, w, cw, x0, y0, h', w' (size of the warped image), r (letterbox scale), index of the
+ *   image's first row in `rows`, number of its rows (the first max_labels are read).  rot [24][2] float64: cos / sin of k * 15 degrees.
+ * Per row: (a) each of the 24 edges vertex k -> k + 1 is cut into 8 equal pieces in source pixel space and the 192 outline points
+ * are mapped as above; (b) the centre is the midpoint of their bounding box if that lies inside the mapped outline (even-odd rule:
+ * edge p -> q is crossed when (p.y > cy) != (q.y > cy) and the crossing's x is > cx), else the map of the old centre, and bit 0 of
+ * the row's flag word is set; (c) each of the 24 rays from the centre takes its nearest intersection with the closed 192-edge
+ * outline by the side-of-line rule of ep24_augment_labels (a ray that meets no edge stays at the centre) and the point is clamped
+ * to [0, w'] x [0, h']; (d) centre and vertices are multiplied by r; (e) the row is dropped unless min(width, height) of the new
+ * vertices is > 1.  out [n][max_labels][51] fp32: the survivors in input order, zero padded; out_count [n]; out_flags
+ * [n][max_labels] int32 beside the output rows.  cand [n][max_labels][51] fp32 and keep [n][max_labels] int32 are scratch (they
+ * need no initialisation).  n == 0 is EP24_OK; n <= 65535. */
+int ep24_sector_labels(const double* rows, const double* geo, const double* rot, int n, int max_labels, float* cand, int32_t* keep,
+                       float* out, int32_t* out_count, int32_t* out_flags, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * N3  inference path: eval-mode network + postprocess
  * ------------------------------------------------------------------------------------------------ */
