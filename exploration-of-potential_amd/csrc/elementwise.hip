@@ -1191,6 +1191,7 @@ extern "C" int ep24_bn_act_fwd(const void* z, int64_t ld_z, const int64_t* stats
                                const float* beta, float* running_mean, float* running_var, int64_t* num_batches,
                                int64_t* num_batches2, float* save, void* y, int64_t ld_y, const void* residual, int64_t ld_res,
                                int64_t M, int C, float eps, float momentum, int act, void* stream) {
+    EP24_REQUIRE(act >= 0 && act <= 3, EP24_E_ARG, "bn_act_fwd: act=%d is none of 0 identity, 1 SiLU, 2 ReLU, 3 LeakyReLU(0.1)", act);
     EP24_REQUIRE(z && stats && gamma && beta && save && y, EP24_E_ARG, "bn_act_fwd: null pointer");
     EP24_REQUIRE(C % 8 == 0 && ld_z % 8 == 0 && ld_y % 8 == 0 && (!residual || ld_res % 8 == 0), EP24_E_ARG,
                  "bn_act_fwd: C=%d / strides must be multiples of 8", C);
@@ -1212,6 +1213,7 @@ extern "C" int ep24_bn_act_fwd(const void* z, int64_t ld_z, const int64_t* stats
 extern "C" int ep24_bn_act_bwd_reduce(const void* dy, int64_t ld_dy, const void* z, int64_t ld_z, const float* save,
                                       const float* gamma, const float* beta, int64_t* dgamma, int64_t* dbeta, int64_t M, int C,
                                       int act, int reps, void* stream) {
+    EP24_REQUIRE(act >= 0 && act <= 3, EP24_E_ARG, "bn_act_bwd_reduce: act=%d is none of 0 identity, 1 SiLU, 2 ReLU, 3 LeakyReLU(0.1)", act);
     EP24_REQUIRE(dy && z && save && gamma && beta && dgamma && dbeta && reps > 0, EP24_E_ARG, "bn_act_bwd_reduce: null pointer / reps");
     EP24_REQUIRE(C % 8 == 0 && ld_dy % 8 == 0 && ld_z % 8 == 0, EP24_E_ARG, "bn_act_bwd_reduce: alignment");
     // 256-thread blocks, two per CU (round 4).  Alone, one 512-thread block per CU is as fast or 0.5 us faster (tools/bn_probe.py,
@@ -1231,6 +1233,7 @@ extern "C" int ep24_bn_act_bwd_apply(const void* dy, int64_t ld_dy, const void* 
                                      const float* gamma, const float* beta, const int64_t* dgamma, const int64_t* dbeta,
                                      float* gamma_grad, float* beta_grad, void* dz, int64_t ld_dz, int64_t M, int C, int act,
                                      int reps, void* stream) {
+    EP24_REQUIRE(act >= 0 && act <= 3, EP24_E_ARG, "bn_act_bwd_apply: act=%d is none of 0 identity, 1 SiLU, 2 ReLU, 3 LeakyReLU(0.1)", act);
     EP24_REQUIRE(dy && z && save && gamma && beta && dgamma && dbeta && dz && reps > 0, EP24_E_ARG, "bn_act_bwd_apply: null pointer / reps");
     EP24_REQUIRE(C % 8 == 0 && ld_dy % 8 == 0 && ld_z % 8 == 0 && ld_dz % 8 == 0, EP24_E_ARG, "bn_act_bwd_apply: alignment");
     EP24_REQUIRE((((uintptr_t)save | (uintptr_t)gamma | (uintptr_t)beta) & 15) == 0, EP24_E_ARG,
@@ -1249,6 +1252,7 @@ extern "C" int ep24_bn_act_bwd_apply(const void* dy, int64_t ld_dy, const void* 
 extern "C" int ep24_bn_act_bwd_fused(const void* dy, int64_t ld_dy, const void* z, int64_t ld_z, const float* save, const float* gamma,
                                      const float* beta, int64_t* dgamma, int64_t* dbeta, float* gamma_grad, float* beta_grad, void* dz,
                                      int64_t ld_dz, int64_t M, int C, int act, int reps, int32_t* barrier, void* stream) {
+    EP24_REQUIRE(act >= 0 && act <= 3, EP24_E_ARG, "bn_act_bwd_fused: act=%d is none of 0 identity, 1 SiLU, 2 ReLU, 3 LeakyReLU(0.1)", act);
     EP24_REQUIRE(dy && z && save && gamma && beta && dgamma && dbeta && dz && barrier && reps > 0, EP24_E_ARG, "bn_act_bwd_fused: null pointer / reps");
     EP24_REQUIRE(C % 8 == 0 && C <= 2048 && ld_dy % 8 == 0 && ld_z % 8 == 0 && ld_dz % 8 == 0, EP24_E_ARG, "bn_act_bwd_fused: alignment / C <= 2048");
     EP24_REQUIRE((((uintptr_t)save | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)gamma_grad | (uintptr_t)beta_grad) & 15) == 0, EP24_E_ARG,
@@ -1274,12 +1278,13 @@ extern "C" int ep24_bn_act_bwd_apply_acc(const void* dy, int64_t ld_dy, const vo
                                          const float* gamma, const float* beta, const int64_t* dgamma, const int64_t* dbeta,
                                          float* gamma_grad, float* beta_grad, void* dz, int64_t ld_dz, int64_t M, int C, int act,
                                          int reps, void* stream) {
+    EP24_REQUIRE(act >= 0 && act <= 3, EP24_E_ARG, "bn_act_bwd_apply_acc: act=%d is none of 0 identity, 1 SiLU, 2 ReLU, 3 LeakyReLU(0.1)", act);
     EP24_REQUIRE(dy && z && save && gamma && beta && dgamma && dbeta && dz && reps > 0, EP24_E_ARG, "bn_act_bwd_apply_acc: null pointer / reps");
     EP24_REQUIRE(C % 8 == 0 && ld_dy % 8 == 0 && ld_z % 8 == 0 && ld_dz % 8 == 0, EP24_E_ARG, "bn_act_bwd_apply_acc: alignment");
     EP24_REQUIRE((((uintptr_t)save | (uintptr_t)gamma | (uintptr_t)beta) & 15) == 0, EP24_E_ARG,
                  "bn_act_bwd_apply_acc: save / gamma / beta must be 16-byte aligned (they are read as vectors)");
     EP24_REQUIRE((((uintptr_t)gamma_grad | (uintptr_t)beta_grad) & 15) == 0, EP24_E_ARG, "bn_act_bwd_apply_acc: gamma_grad / beta_grad must be 16-byte aligned");
-    auto kfn = act == 1 ? bn_act_bwd_apply_kernel<4, 1, true> : act == 2 ? bn_act_bwd_apply_kernel<4, 2, true> : bn_act_bwd_apply_kernel<4, 0, true>;
+    auto kfn = act == 1 ? bn_act_bwd_apply_kernel<4, 1, true> : act == 2 ? bn_act_bwd_apply_kernel<4, 2, true> : act == 3 ? bn_act_bwd_apply_kernel<4, 3, true> : bn_act_bwd_apply_kernel<4, 0, true>;
     hipLaunchKernelGGL(kfn, dim3(rows_grid(M, C, 16, 2048)), dim3(256), 2 * (size_t)C * sizeof(float), S_, (const bf16*)dy, ld_dy, (const bf16*)z, ld_z, save, gamma, beta,
                        (const long long*)dgamma, (const long long*)dbeta, gamma_grad, beta_grad, (bf16*)dz, ld_dz, M, C, reps);
     EP24_LAUNCH_CHECK("ep24_bn_act_bwd_apply_acc");

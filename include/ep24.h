@@ -736,7 +736,8 @@ int ep24_maxpool3s2_bwd(const void* dy, int64_t ld_dy, const uint8_t* idx, void*
 int ep24_colstats(const void* x, int64_t ld, int64_t* stats, int64_t ld_stats, int64_t M, int C, void* stream);
 /* dst[rep][2][C] = the first C channels of src[rep][2][ld_src]. */
 int ep24_stats_gather(const int64_t* src, int64_t ld_src, int64_t* dst, int C, int reps, void* stream);
-/* ep24_bn_act_bwd_apply with dz += instead of dz = (same arguments). */
+/* ep24_bn_act_bwd_apply with dz += instead of dz = (same arguments, every act of 0 .. 3): dz = bf16(float(bf16(new)) + old).
+ * Every ep24_bn_act_* entry point refuses an act outside 0 .. 3 with EP24_E_ARG. */
 /* Round 5: pass 1 and pass 2 as ONE launch (at most one 256-thread workgroup per CU; a grid-wide arrive / wait on *barrier between the
  * passes - an int32 the caller zeroes before the launch; a bounded spin whose give-ups ep24_conv_ring_timeouts counts).  Same sums,
  * same dz, same gradient publication as the two launches. */
