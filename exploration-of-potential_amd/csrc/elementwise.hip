@@ -1370,6 +1370,8 @@ extern "C" int ep24_rows_copy(const void* src, int64_t ld_src, void* dst, int64_
 
 extern "C" int ep24_cast_f32_bf16(const float* src, void* dst, int64_t n, void* stream) {
     EP24_REQUIRE(src && dst && n % 4 == 0 && n >= 0, EP24_E_ARG, "cast_f32_bf16: n must be a multiple of 4");
+    // the kernel moves 4 elements per lane: a 16-byte load and an 8-byte store
+    EP24_REQUIRE((uintptr_t)src % 16 == 0 && (uintptr_t)dst % 8 == 0, EP24_E_ARG, "cast_f32_bf16: src must be 16-byte, dst 8-byte aligned");
     if (n) hipLaunchKernelGGL(cast_f32_bf16_kernel, dim3(cap_grid(n / 4)), dim3(256), 0, S_, src, (bf16*)dst, (long)(n / 4));
     EP24_LAUNCH_CHECK("ep24_cast_f32_bf16");
     return EP24_OK;
@@ -1377,6 +1379,7 @@ extern "C" int ep24_cast_f32_bf16(const float* src, void* dst, int64_t n, void* 
 
 extern "C" int ep24_cast_bf16_f32(const void* src, float* dst, int64_t n, void* stream) {
     EP24_REQUIRE(src && dst && n % 4 == 0 && n >= 0, EP24_E_ARG, "cast_bf16_f32: n must be a multiple of 4");
+    EP24_REQUIRE((uintptr_t)src % 8 == 0 && (uintptr_t)dst % 16 == 0, EP24_E_ARG, "cast_bf16_f32: src must be 8-byte, dst 16-byte aligned");
     if (n) hipLaunchKernelGGL(cast_bf16_f32_kernel, dim3(cap_grid(n / 4)), dim3(256), 0, S_, (const bf16*)src, dst, (long)(n / 4));
     EP24_LAUNCH_CHECK("ep24_cast_bf16_f32");
     return EP24_OK;

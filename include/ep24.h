@@ -176,7 +176,11 @@ int ep24_pack_weights(const float* w, int64_t ld_w, void* w_fwd, void* w_dgrad, 
  * T*ceil(Cout/64)*ceil(Cin/64), the 64x64 tiles of the LDS transpose that writes w_dgrad coalesced.
  * chunk_seg [ceil(total/4096)] int32 = segment of element 4096*c and tile_seg [total_tiles] int32 = segment of tile t are
  * optional lookup tables built once by the host (NULL: the kernels bisect the prefix tables, eight dependent loads per chunk).
- * which: 0 both copies, 1 w_fwd only, 2 w_dgrad only (backward is the first to read it). */
+ * which: 0 both copies, 1 w_fwd only, 2 w_dgrad only (backward is the first to read it).
+ * w_fwd: only real elements are written, as in the single-layer form.  w_dgrad: where a segment's Cout_pad and w_dgrad offset are
+ * multiples of 8 the rows leave as 16-byte stores, so its Cout padding columns (Cout <= co < Cout_pad) MAY be rewritten, and only
+ * with +0 - the caller still zero-initialises them once, and they hold +0 after every call.  Nothing outside a segment's
+ * [Cin][T][Cout_pad] block is written, and nothing of a copy that `which` excludes. */
 int ep24_pack_weights_batched(const float* flat, const int64_t* desc, const int64_t* prefix, const int64_t* tile_prefix,
                               int n_seg, void* w_fwd, void* w_dgrad, int64_t total, int64_t total_tiles,
                               const int32_t* chunk_seg, const int32_t* tile_seg, int which, void* stream);
@@ -338,7 +342,8 @@ int ep24_upsample2_bwd(const void* dy, int64_t ld_dy, void* dx, int64_t ld_dx, i
 /* hipMemsetAsync(p, 0, bytes) on the stream (step-start clearing of gradient / statistics buffers). */
 int ep24_memset_zero(void* p, int64_t bytes, void* stream);
 /* fp32 <-> bf16 casts of n (multiple of 4) contiguous elements: the bf16 wire format of the data-parallel gradient buckets
- * (ep24.dp.GradReducer(comm_dtype=torch.bfloat16): half the xGMI bytes of the reference's fp32 DDP buckets, core/trainer.py:163). */
+ * (ep24.dp.GradReducer(comm_dtype=torch.bfloat16): half the xGMI bytes of the reference's fp32 DDP buckets, core/trainer.py:163).
+ * Four elements move per lane: the fp32 side must be 16-byte aligned and the bf16 side 8-byte aligned, else EP24_E_ARG. */
 int ep24_cast_f32_bf16(const float* src, void* dst, int64_t n, void* stream);
 int ep24_cast_bf16_f32(const void* src, float* dst, int64_t n, void* stream);
 
