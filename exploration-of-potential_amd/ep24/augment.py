@@ -1,4 +1,4 @@
-"""Training augmentation on the GPU for 24-point labels: mosaic, random affine, mirror, HSV (csrc/augment.hip).
+"""Training augmentation on the GPU for 24-point labels: mosaic, random affine, mixup, mirror, HSV (csrc/augment.hip).
 
 The reference's 24p ``TrainTransform`` accepts ``flip_prob`` / ``hsv_prob`` and ignores them, and its mosaic /
 ``random_affine`` code (yolox_24p/data/) transforms boxes only.  Here the raw uint8 images that the prefetcher uploads
@@ -6,10 +6,19 @@ anyway are sampled straight into the network input through the inverse affine ma
 forward and its 24 rays are re-cast from the new centre (``ep24_augment_labels``).
 
 ``sample_params`` draws what stock YOLOX draws (``MosaicDetection.__getitem__``, ``get_affine_matrix``, ``_mirror``,
-``augment_hsv``); ``mosaic_batch`` runs the two launches on explicit parameters; ``MosaicTransform`` is the
-``TrainTransform`` that a ``DataPrefetcher`` takes.  Deviations from the reference, on purpose: the three mosaic partners of
-an image come from the SAME BATCH (the reference draws them from the whole dataset; here nothing extra is uploaded), and
-mixup is not implemented.  There is no CPU fallback.
+``augment_hsv``); ``sample_mixup`` adds ``MosaicDetection.mixup``'s draws from a generator of its own; ``mosaic_batch`` runs
+the two launches on explicit parameters; ``MosaicTransform`` is the ``TrainTransform`` that a ``DataPrefetcher`` takes.
+
+Mixup blends one more source of the batch into a mosaic image, in the same two launches (``ep24_augment_mix_u8`` /
+``ep24_augment_mix_labels``): the partner is letterboxed, its canvas scaled by ``jit``, mirrored, cropped at (x_off, y_off) and
+averaged with the mosaic as ``(a + b) >> 1`` BEFORE HSV; its polygons go through their own map and the same keep and re-cast
+rules, behind the four tiles' rows.
+
+Deviations from the reference, on purpose: the three mosaic partners and the mixup partner of an image come from the SAME BATCH
+(the reference draws them from the whole dataset; here nothing extra is uploaded); the reference mixes only when the mosaic has
+labels left (``len(mosaic_labels) != 0``), which only the GPU knows - here the host-known stand-in is "the four tiles' sources
+have at least one label row between them"; and the partner's pixel is ONE bilinear sample of the raw source, where cv2 resizes
+twice (letterbox, then jitter).  There is no CPU fallback.
 """
 import math
 
@@ -49,7 +58,10 @@ class AugParams:
     2S canvas; ``partners`` int [n,4] = source index of the top-left, top-right, bottom-left, bottom-right tile (column 0
     is the image itself); ``M`` float64 [n,2,3] canvas -> output and ``Minv`` its inverse; ``mirror`` bool [n];
     ``hsv_on`` bool [n]; ``hsv`` float64 [n,3] = gains (dh, ds, dv).  Without mosaic an image is its own single tile,
-    letterboxed at the top left of an S canvas, and ``M`` is whatever the caller sets (``sample_params``: identity)."""
+    letterboxed at the top left of an S canvas, and ``M`` is whatever the caller sets (``sample_params``: identity).
+    Mixup, off by default (``sample_mixup`` fills it): ``mixup`` bool [n]; ``mix_partner`` int [n] = source index of the blended
+    image; ``mix_jit`` float64 [n] = scale of its letterbox canvas; ``mix_flip`` bool [n]; ``mix_off`` int [n,2] = (x_off, y_off),
+    the corner of the S_h x S_w window cut out of the jittered canvas."""
 
     def __init__(self, n):
         self.n = n
@@ -61,6 +73,11 @@ class AugParams:
         self.mirror = np.zeros(n, dtype=bool)
         self.hsv_on = np.zeros(n, dtype=bool)
         self.hsv = np.zeros((n, 3), dtype=np.float64)
+        self.mixup = np.zeros(n, dtype=bool)
+        self.mix_partner = np.arange(n, dtype=np.int64)
+        self.mix_jit = np.ones(n, dtype=np.float64)
+        self.mix_flip = np.zeros(n, dtype=bool)
+        self.mix_off = np.zeros((n, 2), dtype=np.int64)
 
     def set_matrix(self, i, M):
         self.M[i] = np.asarray(M, dtype=np.float64).reshape(2, 3)
@@ -119,6 +136,80 @@ def sample_params(rng, sizes, input_size, mosaic_prob=1.0, degrees=10.0, transla
         p.hsv_on[i] = u_hsv < hsv_prob
         p.hsv[i] = [float(int(g * s)) for g, s in zip(gains, switches)]
     return p
+
+
+def mixup_rng(seed, epoch, it):
+    """The generator of the mixup draws of batch (epoch, it): its own stream, so ``sample_params``' draws do not move."""
+    return np.random.RandomState(np.array([seed, epoch, it, 1], dtype=np.uint32))
+
+
+def mixup_canvas(jit, input_size):
+    """(Wj, Hj) = the partner's letterbox canvas after the jitter: int(S_w*jit), int(S_h*jit), as the reference's cv2.resize."""
+    Wj, Hj = int(int(input_size[1]) * jit), int(int(input_size[0]) * jit)
+    if Wj < 1 or Hj < 1:
+        raise ValueError("mixup: a jitter of %r leaves an empty %d x %d canvas" % (jit, Wj, Hj))
+    return Wj, Hj
+
+
+def sample_mixup(rng, params, sizes, label_counts, input_size, mixup_prob=1.0, mixup_scale=(0.5, 1.5)):
+    """Fills the mixup fields of ``params`` (an ``AugParams`` for ``len(sizes)`` images) from ``rng`` (``mixup_rng``) and returns
+    ``params``.  ``label_counts``: label rows per source image.
+
+    Per output image, in this order and ALWAYS all 6 numbers:
+      1  u_mix   = random_sample()              wanted if u_mix < mixup_prob
+      2  jit     = uniform(*mixup_scale)
+      3  u_flip  = random_sample()              flip if u_flip > 0.5
+      4  partner = randint(0, n)
+      5  u_y, 6 u_x = random_sample()           y_off = int(u_y*(Hj - S_h)) if Hj > S_h else 0, x likewise: randint(0, Hj-S_h-1)'s range
+    Mixup is ON for image i iff it is wanted, the image is a mosaic, a partner with labels exists (the drawn index, else the next
+    one cyclically that has label rows; none in the batch: no mixup) and the four tiles' sources have a label row between them
+    (the host-known stand-in for the reference's ``len(mosaic_labels) != 0``)."""
+    n = len(sizes)
+    if params.n != n or len(label_counts) != n:
+        raise ValueError("sample_mixup: %d sizes, %d label counts, parameters for %d" % (n, len(label_counts), params.n))
+    S_h, S_w = int(input_size[0]), int(input_size[1])
+    has = [int(c) > 0 for c in label_counts]
+    for i in range(n):
+        u_mix = rng.random_sample()
+        jit = rng.uniform(mixup_scale[0], mixup_scale[1])
+        u_flip = rng.random_sample()
+        partner = int(rng.randint(0, n))
+        u_y, u_x = rng.random_sample(), rng.random_sample()
+        params.mixup[i] = False
+        if not (u_mix < mixup_prob and params.mosaic[i] and any(has) and any(has[int(j)] for j in params.partners[i])):
+            continue
+        while not has[partner]:
+            partner = (partner + 1) % n
+        Wj, Hj = mixup_canvas(jit, (S_h, S_w))
+        params.mixup[i] = True
+        params.mix_partner[i], params.mix_jit[i], params.mix_flip[i] = partner, jit, u_flip > 0.5
+        params.mix_off[i] = (int(u_x * (Wj - S_w)) if Wj > S_w else 0, int(u_y * (Hj - S_h)) if Hj > S_h else 0)
+    return params
+
+
+def mixup_layout(params, i, sizes, input_size):
+    """The mixup descriptor of output image i as the kernels take it (include/ep24.h): (int64 [16] without the byte offset and
+    the label rows, float64 [12]), or None when mixup is off for the image."""
+    if not params.mixup[i]:
+        return None
+    S_h, S_w = int(input_size[0]), int(input_size[1])
+    j = int(params.mix_partner[i])
+    h, w = sizes[j]
+    s, rh, rw = letterbox_geometry(h, w, (S_h, S_w))
+    Wj, Hj = mixup_canvas(float(params.mix_jit[i]), (S_h, S_w))
+    x_off, y_off = int(params.mix_off[i][0]), int(params.mix_off[i][1])
+    flip = bool(params.mix_flip[i])
+    if x_off < 0 or y_off < 0:
+        raise ValueError("mixup: negative crop offset (%d, %d)" % (x_off, y_off))
+    if rw <= 0 or rh <= 0:
+        raise ValueError("mixup: the partner's letterbox is empty")
+    ints = np.zeros(16, dtype=np.int64)
+    ints[:12] = (1, 0, h, w, 3 * w, rw, rh, Wj, Hj, x_off, y_off, int(flip))
+    a00, a11 = (-(Wj / S_w) if flip else Wj / S_w), Hj / S_h
+    dbl = np.zeros(12, dtype=np.float64)
+    dbl[:11] = (S_w / Wj, S_h / Hj, 1.0 / (rw / w), 1.0 / (rh / h), s, a00, a11, float(Wj - x_off if flip else -x_off),
+                float(-y_off), 1.0 / a00, 1.0 / a11)
+    return ints, dbl
 
 
 def tile_layout(params, i, sizes, input_size):
@@ -198,6 +289,8 @@ def mosaic_batch(images, targets, params, input_size, max_labels=50, out_images=
     if row_off[-1]:
         dbl[n * 28:] = np.concatenate(rows, 0).reshape(-1)
     flags = np.zeros((n, 2), dtype=np.int32)
+    mixing = bool(np.asarray(params.mixup).any())
+    mix_i, mix_d = np.zeros((n, 16), dtype=np.int64), np.zeros((n, 12), dtype=np.float64)
     for i in range(n):
         for q, (j, rw, rh, (lx1, ly1, lx2, ly2), padw, padh) in enumerate(tile_layout(params, i, sizes, (S_h, S_w))):
             h, w = sizes[j]
@@ -209,13 +302,28 @@ def mosaic_batch(images, targets, params, input_size, max_labels=50, out_images=
         par[i, 6:12] = params.Minv[i].reshape(6)
         par[i, 12:15] = params.hsv[i]
         flags[i] = (int(params.mirror[i]), int(params.hsv_on[i]))
-    if not (np.isfinite(par).all() and np.isfinite(tsc).all()):
+        if params.mixup[i]:
+            j = int(params.mix_partner[i])
+            if not 0 <= j < n:
+                raise ValueError("mosaic_batch: mixup partner %d of image %d is not in the batch" % (j, i))
+            mix_i[i], mix_d[i] = mixup_layout(params, i, sizes, (S_h, S_w))
+            mix_i[i, 1], mix_i[i, 12], mix_i[i, 13] = offs[j], row_off[j], row_off[j + 1]
+    if not (np.isfinite(par).all() and np.isfinite(tsc).all() and np.isfinite(mix_d).all()):
         raise ValueError("mosaic_batch: non-finite parameters")
     buf = torch.cat([f.to(dev, non_blocking=True) for f in flat])
     tiles_t = torch.from_numpy(tiles).to(dev)
     dbl_t = torch.from_numpy(dbl).to(dev)
     flags_t = torch.from_numpy(flags).to(dev)
     rot = _rot(dev)
+    if mixing:
+        mi_t, md_t = torch.from_numpy(mix_i).to(dev), torch.from_numpy(mix_d).to(dev)
+        for lo in range(0, n, 65535):
+            hi = min(n, lo + 65535)
+            call("augment_mix_u8", ptr(buf), ptr(tiles_t, lo * 64), ptr(dbl_t, lo * 12), ptr(dbl_t, n * 12 + lo * 16), ptr(flags_t, lo * 2),
+                 ptr(mi_t, lo * 16), ptr(md_t, lo * 12), hi - lo, ptr(out_images, lo * 3 * S_h * S_w), S_h, S_w, stream_ptr())
+        call("augment_mix_labels", ptr(dbl_t, n * 28), ptr(tiles_t), ptr(dbl_t), ptr(dbl_t, n * 12), ptr(flags_t), ptr(mi_t), ptr(md_t),
+             ptr(rot), n, S_h, S_w, float(min_margin), ptr(out_labels), ptr(counts), max_labels, stream_ptr())
+        return out_images, out_labels, counts
     for lo in range(0, n, 65535):
         hi = min(n, lo + 65535)
         call("augment_u8", ptr(buf), ptr(tiles_t, lo * 64), ptr(dbl_t, lo * 12), ptr(dbl_t, n * 12 + lo * 16), ptr(flags_t, lo * 2),
@@ -229,36 +337,47 @@ class MosaicTransform(TrainTransform):
     """``TrainTransform`` with the augmentation switched on: same ``batch(...)`` signature, so ``DataPrefetcher`` takes it
     unchanged.  ``enabled = False`` makes it the plain transform (the last ``no_aug_epochs`` of a YOLOX run).
     ``set_position(epoch, it)`` reseeds the generator from (seed, epoch, it): the batch at a data position gets the same
-    parameters whenever it is produced, so a resumed run reproduces the batches it would have seen."""
+    parameters whenever it is produced, so a resumed run reproduces the batches it would have seen.  ``mixup_prob > 0`` adds
+    mixup (``sample_mixup``, from a generator of its own at the same position); with 0 the transform is what it is without."""
 
     def __init__(self, max_labels=50, flip_prob=0.5, hsv_prob=1.0, mosaic_prob=1.0, degrees=10.0, translate=0.1,
-                 mosaic_scale=(0.5, 1.5), shear=2.0, min_margin=2.0, seed=0, enabled=True):
+                 mosaic_scale=(0.5, 1.5), shear=2.0, min_margin=2.0, seed=0, enabled=True, mixup_prob=0.0,
+                 mixup_scale=(0.5, 1.5)):
         super().__init__(max_labels=max_labels, flip_prob=flip_prob, hsv_prob=hsv_prob, seed=seed)
         self.hsv_prob, self.mosaic_prob, self.degrees, self.translate = hsv_prob, mosaic_prob, degrees, translate
         self.mosaic_scale, self.shear, self.min_margin = tuple(mosaic_scale), shear, min_margin
         self.seed, self.enabled = int(seed), enabled
+        self.mixup_prob, self.mixup_scale = mixup_prob, tuple(mixup_scale)
         self.last_params = self.last_counts = None
         self.set_position(0, 0)
 
     @classmethod
-    def from_exp(cls, exp, max_labels=50, seed=0):
+    def from_exp(cls, exp, max_labels=50, seed=0, mixup=False):
+        """``mixup=True`` reads the Exp's ``mixup_prob`` / ``mixup_scale`` (``train_24p.py --mixup``); otherwise mixup stays off."""
+        extra = dict(mixup_prob=exp.mixup_prob, mixup_scale=exp.mixup_scale) if mixup else {}
         return cls(max_labels=max_labels, flip_prob=exp.flip_prob, hsv_prob=exp.hsv_prob, mosaic_prob=exp.mosaic_prob,
-                   degrees=exp.degrees, translate=exp.translate, mosaic_scale=exp.mosaic_scale, shear=exp.shear, seed=seed)
+                   degrees=exp.degrees, translate=exp.translate, mosaic_scale=exp.mosaic_scale, shear=exp.shear, seed=seed, **extra)
 
     def set_position(self, epoch, it):
         self.position = (int(epoch), int(it))
         self._aug_rng = position_rng(self.seed, epoch, it)
+        self._mix_rng = mixup_rng(self.seed, epoch, it)
 
-    def sample(self, sizes, input_dim):
-        return sample_params(self._aug_rng, sizes, input_dim, mosaic_prob=self.mosaic_prob, degrees=self.degrees,
-                             translate=self.translate, mosaic_scale=self.mosaic_scale, shear=self.shear,
-                             flip_prob=self.flip_prob, hsv_prob=self.hsv_prob)
+    def sample(self, sizes, input_dim, label_counts=None):
+        """The parameters of the next batch; mixup needs ``label_counts`` (label rows per source) and is left off without."""
+        p = sample_params(self._aug_rng, sizes, input_dim, mosaic_prob=self.mosaic_prob, degrees=self.degrees,
+                          translate=self.translate, mosaic_scale=self.mosaic_scale, shear=self.shear,
+                          flip_prob=self.flip_prob, hsv_prob=self.hsv_prob)
+        if self.mixup_prob > 0 and label_counts is not None:
+            sample_mixup(self._mix_rng, p, sizes, label_counts, input_dim, mixup_prob=self.mixup_prob, mixup_scale=self.mixup_scale)
+        return p
 
     def batch(self, images, targets, input_dim, out_images=None, out_labels=None):
         if not self.enabled:
             return super().batch(images, targets, input_dim, out_images=out_images, out_labels=out_labels)
         _lib.require_gpu()
-        params = self.sample([tuple(im.shape[:2]) for im in images], input_dim)
+        params = self.sample([tuple(im.shape[:2]) for im in images], input_dim,
+                             [np.asarray(t).size // 51 for t in targets])
         imgs, labs, counts = mosaic_batch(images, targets, params, input_dim, self.max_labels, out_images, out_labels,
                                           min_margin=self.min_margin)
         self.last_params, self.last_counts = params, counts

@@ -34,6 +34,9 @@ class Exp(BaseExp):
         self.shear = 2.0
         self.flip_prob = 0.5
         self.hsv_prob = 1.0
+        self.enable_mixup = True         # with train_24p.py --mixup (ep24.augment.sample_mixup); stock YOLOX's names and values
+        self.mixup_prob = 1.0
+        self.mixup_scale = (0.5, 1.5)
         # training
         self.warmup_epochs = 5
         self.max_epoch = 300

@@ -70,6 +70,7 @@ class Trainer:
         args.raw_u8 = not (args.fp32_batches or args.no_prefetch)
         if args.augment and not args.raw_u8:
             raise SystemExit("train_24p.py: --augment works on the raw uint8 batches behind the prefetcher (drop --no-prefetch / --fp32-batches)")
+        check_mixup_args(args)
         if args.fisheye_theta is not None:
             check_fisheye_args(args)
         self.train_loader = exp.get_data_loader(args.batch_size, raw_u8=bool(args.raw_u8), workers=args.loader_workers,
@@ -313,10 +314,12 @@ class Trainer:
     def augment_transform(self):
         """--augment: ONE ``MosaicTransform`` for the run (the Exp's mosaic_prob / degrees / translate / mosaic_scale / shear /
         flip_prob / hsv_prob), switched on for epochs < max_epoch - no_aug_epochs and off after - what ``no_aug_epochs`` means in
-        YOLOX (core/trainer.py before_epoch: close_mosaic)."""
+        YOLOX (core/trainer.py before_epoch: close_mosaic).  --mixup adds the Exp's mixup_prob / mixup_scale iff exp.enable_mixup;
+        mixup goes off with the rest."""
         if getattr(self, "transform", None) is None:
             from datasets import MosaicTransform
-            self.transform = MosaicTransform.from_exp(self.exp, max_labels=50, seed=self.args.augment_seed)
+            mixup = bool(getattr(self.args, "mixup", False) and self.exp.enable_mixup)
+            self.transform = MosaicTransform.from_exp(self.exp, max_labels=50, seed=self.args.augment_seed, mixup=mixup)
         self.transform.enabled = self.epoch < self.max_epoch - self.exp.no_aug_epochs
         return self.transform
 
@@ -364,6 +367,12 @@ class Trainer:
         if self.ema_model is not None:
             state["ema_model"], state["ema_updates"] = self.ema_model.ema.state_dict(), self.ema_model.updates
         save_checkpoint(state, update_best_ckpt, self.file_name, ckpt_name)
+
+
+def check_mixup_args(args):
+    """--mixup blends a second image into the mosaic images of --augment: it needs --augment."""
+    if getattr(args, "mixup", False) and not args.augment:
+        raise SystemExit("train_24p.py: --mixup blends a second image into the mosaic of --augment (add --augment)")
 
 
 def check_fisheye_args(args):
@@ -416,6 +425,9 @@ def make_parser():
     p.add_argument("--augment", action="store_true", help="mosaic, random affine, mirror and HSV on the GPU for 24-point labels (ep24.augment."
                    "MosaicTransform behind the prefetcher) with the Exp's mosaic_prob / degrees / translate / mosaic_scale / shear / flip_prob / "
                    "hsv_prob, for epochs < max_epoch - no_aug_epochs")
+    p.add_argument("--mixup", action="store_true", help="with --augment: mixup on the GPU (a second image of the batch, letterboxed, "
+                   "jittered, mirrored and cropped, averaged into every mosaic image; its 24-point labels re-cast and appended) with the "
+                   "Exp's mixup_prob / mixup_scale, iff exp.enable_mixup")
     p.add_argument("--augment-seed", default=0, type=int, help="seed of the augmentation; a batch's parameters follow from (seed, epoch, iteration)")
     p.add_argument("--fisheye-theta", default=None, type=int, nargs=2, metavar=("LO", "HI"), help="fisheye sector warp of every image AND its "
                    "24-point labels on the GPU (ep24.fisheye.FisheyeTransform behind the prefetcher), one angle in [LO, HI] degrees per image, "

@@ -682,7 +682,7 @@ int ep24_preproc_u8(const uint8_t* images, const int64_t* desc, const double* sc
 int ep24_preproc_labels(const double* rows, const int64_t* row_off, const double* whr, int n, float* out, int max_labels,
                         void* stream);
 
-/* Training augmentation (mosaic, random affine, mirror, HSV), two launches per batch.  Every output image
+/* Training augmentation (mosaic, random affine, mixup, mirror, HSV), two launches per batch.  Every output image
  * is assembled from up to four TILES: a tile is one source image, resized by s = min(S_h/h, S_w/w) as preproc resizes it and
  * placed on a canvas (2 S_h x 2 S_w with four tiles for a mosaic; S_h x S_w with one tile at the top left without).  Shared inputs:
  *   tiles[n][4][16] int64 = {0 byte offset of the source in `images`, 1 h, 2 w, 3 row stride in bytes, 4 rw = int(w*s),
@@ -713,6 +713,30 @@ int ep24_augment_u8(const uint8_t* images, const int64_t* tiles, const double* t
 int ep24_augment_labels(const double* rows, const int64_t* tiles, const double* tile_scales, const double* params,
                         const int32_t* flags, const double* rot, int n, int S_h, int S_w, double min_margin, float* out,
                         int32_t* out_count, int max_labels, void* stream);
+/* Mixup (MosaicDetection.mixup) fused into the same two launches: every argument of the sibling above, plus one descriptor per
+ * output image.  An image whose descriptor has on == 0 comes out bit-identical to ep24_augment_u8 / ep24_augment_labels.
+ *   mix[n][16] int64 = {0 on, 1 byte offset of the partner source in `images`, 2 h, 3 w, 4 row stride in bytes, 5 rw = int(w*s),
+ *       6 rh = int(h*s), 7 Wj = int(S_w*jit), 8 Hj = int(S_h*jit) (the jittered canvas, both >= 1), 9 x_off, 10 y_off (>= 0: the
+ *       crop window's corner on the jittered canvas), 11 flip, 12 row_lo, 13 row_hi (the partner's label rows in `rows`),
+ *       14, 15 reserved (0)};
+ *   mix_scales[n][12] double = {0 S_w/Wj, 1 S_h/Hj, 2 1/(rw/w), 3 1/(rh/h), 4 s, 5 a00 = flip ? -Wj/S_w : Wj/S_w, 6 a11 = Hj/S_h,
+ *       7 t0 = flip ? Wj - x_off : -x_off, 8 t1 = -y_off, 9 1/a00, 10 1/a11, 11 reserved (0)}.
+ * ep24_augment_mix_u8: with a = the pixel of ep24_augment_u8 BEFORE HSV as an integer (114 where no tile owns it) and
+ * px = xm + x_off, py = y + y_off: the partner value b is 0 if px >= Wj or py >= Hj; otherwise pxf = flip ? Wj-1-px : px,
+ * u = (pxf+0.5)*(S_w/Wj) - 0.5, v = (py+0.5)*(S_h/Hj) - 0.5 in double, and b is ONE fixed-point bilinear sample of the partner at
+ * fx = (u+0.5)*scale_x - 0.5 (fy likewise; a tile with padw = padh = 0) if -0.5 <= u < rw-0.5 and -0.5 <= v < rh-0.5, else 114.
+ * The output is (a + b) >> 1 per channel (0.5*a + 0.5*b truncated to uint8), then HSV on the pixels that a tile or the partner
+ * image owns, then the store.  cv2 would resize twice (letterbox, jitter); here the pixel is one sample of the raw source. */
+int ep24_augment_mix_u8(const uint8_t* images, const int64_t* tiles, const double* tile_scales, const double* params,
+                        const int32_t* flags, const int64_t* mix, const double* mix_scales, int n, float* out, int S_h, int S_w,
+                        void* stream);
+/* The label half with the partner as a fifth candidate source behind the four tiles (the first max_labels of its rows): canvas
+ * X = (v*w)*s, Y = (v*h)*s; output (a00*X + t0, a11*Y + t1), mirrored like every other row; region [0,rw] x [0,rh] for the
+ * centre margin and for the ray's exit (along (d_x/a00, d_y/a11), x negated first when mirrored).  Keep rules, re-cast, order,
+ * cap and count as ep24_augment_labels. */
+int ep24_augment_mix_labels(const double* rows, const int64_t* tiles, const double* tile_scales, const double* params,
+                            const int32_t* flags, const int64_t* mix, const double* mix_scales, const double* rot, int n, int S_h,
+                            int S_w, double min_margin, float* out, int32_t* out_count, int max_labels, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * C4  swapped backbones (yolox_24p/models/darknet.py:179-429, yolox/models/yolo_pafpn.py:31-38; BASELINE config 4)
