@@ -384,7 +384,9 @@ int ep24_colsum_slab(const void* g, int64_t ld, float* slab, int64_t M, int N, v
 int ep24_assign_candidates(const float* labels, const float* xs, const float* ys, const float* strides,
                            int32_t* num_gt, uint64_t* in_box, uint64_t* in_ctr, int B, int A, void* stream);
 /* a6+a7 (bboxes_iou + class cost + total cost, boxes.py:166-243, losses.py:396-424) for every candidate
- * anchor: pw[B,50,A] and cost[B,50,A] fp32 (entries of non-candidate anchors / g >= num_gt are untouched). */
+ * anchor: pw[B,50,A] and cost[B,50,A] fp32 (entries of non-candidate anchors / g >= num_gt are untouched).
+ * At most 96 classes (the class terms of a workgroup's 64 anchors share its 24 x 256 floats of ray scratch): num_classes > 96
+ * returns EP24_E_UNSUPPORTED before any launch and writes nothing; so does ep24_assign_cost_range. */
 int ep24_assign_cost(const float* outputs, int ncols, const float* labels, const int32_t* num_gt,
                      const uint64_t* in_box, const uint64_t* in_ctr, float* pw, float* cost, int B, int A,
                      int num_classes, void* stream);
@@ -395,7 +397,12 @@ int ep24_assign_cost_range(const float* outputs, int ncols, const float* labels,
                            const uint64_t* in_box, const uint64_t* in_ctr, float* pw, float* cost, int B, int A,
                            int num_classes, int a_lo, int a_hi, void* stream);
 /* a8 part 1 (dynamic_k_matching, losses.py:449-464): per (image, gt) top-10 pw sum -> k, the k cheapest
- * candidates are OR-ed into match[B*A] (uint64 bit g).  match must be zeroed by the caller; ks[B,50] out. */
+ * candidates are OR-ed into match[B*A] (uint64 bit g).  match must be zeroed by the caller; ks[B,50] out.
+ * The candidate set is the IMAGE's: every anchor with any bit in in_box | in_ctr, whichever label set it (the reference's fg_mask),
+ * P of them.  The min(10, P) largest pw are taken by (value descending, anchor ascending) and summed in that order in fp32,
+ * k = max(1, trunc(sum)), and the min(k, P) smallest cost are taken by (value ascending, anchor ascending): on equal values the
+ * lower anchor index wins, in both selections.  pw / cost of non-candidate anchors are read and dropped (they may hold anything);
+ * nothing of g >= num_gt[b] is written - neither ks[b][g] nor bit g of match. */
 int ep24_dynamic_k(const float* pw, const float* cost, const int32_t* num_gt, const uint64_t* in_box,
                    const uint64_t* in_ctr, uint64_t* match, int32_t* ks, int B, int A, void* stream);
 /* a8 part 2 (losses.py:471-493): conflicts -> argmin cost, final fg mask, matched gt index (-1 = bg),
