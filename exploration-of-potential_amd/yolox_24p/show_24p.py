@@ -1,0 +1,197 @@
+"""Inference entry point with the reference's flags (yolox_24p/show_24p.py:370-385): run a trained model over a folder of images and
+save every image with its 24-point detections drawn on it.
+
+    cd exploration-of-potential_amd/yolox_24p
+    python show_24p.py -f load_train/yolox_24p_l_train.py -p demo_images -w YOLOX_outputs/yolox_24p_l/last_epoch_ckpt.pth
+
+``Exp.get_model()``, the checkpoint's ``"model"`` entry (``-w``), ``eval()``; then batches of ``-b`` files go through
+``ep24.input.preproc_batch`` (letterbox on the GPU), ``model(images, train=False)``, ``ep24.infer.postprocess`` and
+``ep24.draw.draw_detections`` on the ORIGINAL image with the letterbox ratio - the reference's ``Evaluator.eval`` /
+``save_eval_results`` / ``vis`` (:266-367) without the host-side OpenCV.  Results go to ``<output_dir>/<timestamp>/``: the drawn
+image under its own name, ``<name>.dets.npy`` with the ``[n, 29]`` float32 rows beside it, and one ``detections.json`` (file, size,
+ratio, count).  ``.npy`` (uint8 HWC) and binary PPM are read and written natively; JPEG / PNG when PIL is installed.
+"""
+import argparse
+import json
+import os
+import time
+
+import _path  # noqa: F401
+import numpy as np
+import torch
+
+from exp import get_exp
+
+NATIVE_EXT = (".npy", ".ppm")
+PIL_EXT = (".jpg", ".jpeg", ".png", ".bmp")
+
+
+def _pil():
+    try:
+        from PIL import Image
+        return Image
+    except Exception:                                       # PIL is optional
+        return None
+
+
+def read_ppm(path):
+    """Binary PPM (P6, maxval 255) -> uint8 [h, w, 3]."""
+    data = open(path, "rb").read()
+    fields, pos = [], 0
+    while len(fields) < 4:                                  # magic, width, height, maxval: whitespace-separated, '#' comments
+        while data[pos:pos + 1].isspace():
+            pos += 1
+        if data[pos:pos + 1] == b"#":
+            pos = data.index(b"\n", pos) + 1
+            continue
+        end = pos
+        while not data[end:end + 1].isspace():
+            end += 1
+        fields.append(data[pos:end])
+        pos = end
+    if fields[0] != b"P6" or int(fields[3]) != 255:
+        raise ValueError("%s: only binary PPM (P6) with maxval 255 is read" % path)
+    w, h = int(fields[1]), int(fields[2])
+    pix = np.frombuffer(data, dtype=np.uint8, count=h * w * 3, offset=pos + 1)
+    return pix.reshape(h, w, 3).copy()
+
+
+def write_ppm(path, img):
+    with open(path, "wb") as fh:
+        fh.write(b"P6\n%d %d\n255\n" % (img.shape[1], img.shape[0]))
+        fh.write(np.ascontiguousarray(img, dtype=np.uint8).tobytes())
+
+
+def read_image(path):
+    ext = os.path.splitext(path)[1].lower()
+    if ext == ".npy":
+        img = np.load(path, allow_pickle=False)
+    elif ext == ".ppm":
+        img = read_ppm(path)
+    else:
+        Image = _pil()
+        if Image is None:
+            raise SystemExit("show_24p.py: %s needs PIL, which is not installed (.npy and .ppm are read natively)" % path)
+        img = np.asarray(Image.open(path).convert("RGB"))
+    if img.ndim != 3 or img.shape[2] != 3 or img.dtype != np.uint8:
+        raise SystemExit("show_24p.py: %s is not a uint8 [h, w, 3] image (got %s %s)" % (path, img.shape, img.dtype))
+    return np.ascontiguousarray(img)
+
+
+def write_image(path, img):
+    ext = os.path.splitext(path)[1].lower()
+    if ext == ".npy":
+        np.save(path, img)
+    elif ext == ".ppm":
+        write_ppm(path, img)
+    else:
+        _pil().fromarray(img).save(path)
+
+
+def list_images(load_path):
+    """The image files of a folder (sorted), or the one file given."""
+    exts = NATIVE_EXT + (PIL_EXT if _pil() is not None else ())
+    if os.path.isfile(load_path):
+        return os.path.dirname(load_path) or ".", [os.path.basename(load_path)]
+    if not os.path.isdir(load_path):
+        raise SystemExit("show_24p.py: -p %s is neither a folder nor a file" % load_path)
+    files = sorted(f for f in os.listdir(load_path) if f.lower().endswith(exts) and not f.endswith(".dets.npy"))
+    return load_path, files
+
+
+def read_class_names(path):
+    with open(path) as fh:
+        return [ln.rstrip("\n") for ln in fh if ln.strip()]
+
+
+class Evaluator:
+    def __init__(self, exp, args):
+        self.exp, self.args = exp, args
+        self.num_classes = exp.num_classes
+        dev = torch.device(args.device)
+        if dev.type != "cuda":
+            from ep24._lib import Ep24Error
+            raise Ep24Error("show_24p.py --device %s: the ep24 path runs on an MI355X only (no CPU fallback)" % args.device)
+        self.device = torch.device("cuda", dev.index if dev.index is not None else args.start_device)
+        self.input_size = tuple(exp.test_size)
+        if args.load_path is None:
+            raise SystemExit("show_24p.py: -p / --load_path is required")
+        self.folder, self.file_list = list_images(args.load_path)
+        self.class_names = read_class_names(args.class_names) if args.class_names else None
+        if self.class_names is not None and len(self.class_names) < self.num_classes:
+            raise SystemExit("show_24p.py: --class-names has %d lines for %d classes" % (len(self.class_names), self.num_classes))
+
+    @torch.no_grad()
+    def eval(self):
+        from ep24.draw import draw_detections
+        from ep24.infer import postprocess
+        from ep24.input import preproc_batch
+        args = self.args
+        torch.cuda.set_device(self.device)
+        model = self.exp.get_model()
+        if args.weights:
+            from utils import load_ckpt
+            ck = torch.load(args.weights, map_location="cpu")
+            load_ckpt(model, ck.get("model", ck))
+        else:
+            print("show_24p.py: no -w / --weights: the model keeps its initial parameters")
+        model.to(self.device)
+        model.eval()
+        self.save_folder = os.path.join(args.output_dir or self.exp.output_dir, time.strftime("%Y_%m_%d_%H_%M_%S", time.localtime()))
+        os.makedirs(self.save_folder, exist_ok=True)
+        records = []
+        step = max(int(args.batch_size), 1)
+        for lo in range(0, len(self.file_list), step):
+            names = self.file_list[lo:lo + step]
+            originals = [torch.from_numpy(read_image(os.path.join(self.folder, f))).to(self.device) for f in names]
+            images, ratios = preproc_batch(originals, self.input_size, device=self.device)
+            outputs = postprocess(model(images, train=False), self.num_classes, conf_thre=args.conf, nms_thre=args.nms,
+                                  nms_iou=args.nms_iou)
+            for name, img, ratio, dets in zip(names, originals, ratios, outputs):
+                drawn = draw_detections(img, dets, ratio=ratio, conf=args.draw_conf, num_classes=self.num_classes,
+                                        class_names=self.class_names, fill_alpha=args.fill_alpha, show_scores=args.show_scores)
+                rows = np.zeros((0, 29), dtype=np.float32) if dets is None else dets.float().cpu().numpy()
+                write_image(os.path.join(self.save_folder, name), drawn.cpu().numpy())
+                np.save(os.path.join(self.save_folder, name + ".dets.npy"), rows)
+                records.append({"file": name, "height": int(img.shape[0]), "width": int(img.shape[1]), "ratio": float(ratio),
+                                "count": int(rows.shape[0])})
+                print("%s: %d detections" % (name, rows.shape[0]))
+        with open(os.path.join(self.save_folder, "detections.json"), "w") as fh:
+            json.dump({"input_size": list(self.input_size), "conf": args.conf, "nms": args.nms, "nms_iou": args.nms_iou,
+                       "draw_conf": args.draw_conf, "images": records}, fh, indent=1)
+        print("saved %d images to %s" % (len(records), self.save_folder))
+        return self.save_folder
+
+
+def make_parser():
+    p = argparse.ArgumentParser("YOLOX show parser")
+    p.add_argument("-b", "--batch_size", type=int, default=64, help="batch size")
+    p.add_argument("-s", "--start_device", default=0, type=int, help="device for start count")
+    p.add_argument("-d", "--devices", default=1, type=int, help="number of devices (one is used)")
+    p.add_argument("-f", "--exp_file", default=None, type=str, help="plz input your experiment description file")
+    p.add_argument("-p", "--load_path", type=str, default=None, help="plz input your file path (a folder of images, or one image)")
+    p.add_argument("-w", "--weights", type=str, default=None, help="plz input your weights path")
+    # additions of this build
+    p.add_argument("--output-dir", default=None, type=str, help="results go to <output-dir>/<timestamp>/ (default: exp.output_dir)")
+    p.add_argument("--conf", default=0.01, type=float, help="postprocess: obj * class_conf threshold (the reference's 0.01)")
+    p.add_argument("--nms", default=0.3, type=float, help="postprocess: NMS IoU threshold (the reference's 0.3)")
+    p.add_argument("--nms-iou", default="rect", choices=["rect", "poly24"], help="NMS by the reference's rectangles or by the "
+                   "exact area IoU of the 24-point polygons")
+    p.add_argument("--draw-conf", default=1e-4, type=float, help="detections below this score are not drawn (the reference's 0.0001)")
+    p.add_argument("--fill-alpha", default=0, type=int, help="0..255: blend the class colour over the polygon's inside (0 = outline only)")
+    p.add_argument("--show-scores", action="store_true", help="append the score's two decimals to the label")
+    p.add_argument("--class-names", default=None, type=str, help="a file with one class name per line (default: the class index)")
+    p.add_argument("--device", default="cuda", type=str, help="cuda or cuda:N (the ep24 path has no CPU fallback: cpu is refused)")
+    return p
+
+
+def main(exp, args):
+    ev = Evaluator(exp, args)
+    ev.eval()
+    return ev
+
+
+if __name__ == "__main__":
+    args = make_parser().parse_args()
+    exp = get_exp(args.exp_file)
+    main(exp, args)

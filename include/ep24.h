@@ -661,6 +661,54 @@ int ep24_mask_iou(const uint32_t* a_bits, const int32_t* a_bbox, const int32_t* 
                   const int32_t* b_bbox, const int32_t* b_area, int D, int H, int W, int64_t* inter, double* iou, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * E3  drawing 24-point detections onto an image (csrc/draw.hip; ep24.draw.draw_detections).  The reference's
+ *     Evaluator.vis (show_24p.py:325-367) draws, in the class colour, a filled centre dot of radius 4, a dot of radius 2 on each of
+ *     the 24 points, the closed 24-gon with lines of thickness 2 and the class name next to the centre, after bboxes /= ratio,
+ *     truncation of centre and radii to int and clipping of each vertex to [0, W] x [0, H].  That integer geometry is kept; the pixel
+ *     rules are this library's own and exact (cv2's Bresenham lines and Hershey text cannot be reproduced without cv2: the deviation).
+ *     Image uint8 [H][W][3], contiguous, channel order left alone, 1 <= H, W <= EP24_DRAW_MAX_SIDE; the centre of pixel (x, y) is the
+ *     point (x, y).  det [n][29] = the rows of postprocess (cx, cy, 24 radii, obj, class_conf, class), n >= 0.
+ *   Row geometry (fp32, every operation separate, then truncation toward zero): xc = (int)(cx / ratio), yc = (int)(cy / ratio),
+ *     r_k = (int)(rad_k / ratio), vx_k = (int)min(max((float)xc + (float)r_k * cs[k], 0), (float)W), vy_k the same with cs[24 + k]
+ *     and H; cs = ray_cs[48] (cos, then sin of 15 deg * k, fp32); score = obj * class_conf (fp32); cls = (int)col28.
+ *   A row is skipped (draws nothing) if !(score >= conf), or any of cx / ratio, cy / ratio, rad_k / ratio is non-finite or has
+ *     magnitude >= 2^20, or cls is not in [0, num_classes).
+ *   Solid coverage of pixel X = (x, y) by a row, all in int64 - any of:
+ *     centre disc   (x - xc)^2 + (y - yc)^2 <= 16;
+ *     vertex discs  (x - vx_k)^2 + (y - vy_k)^2 <= 4 for some k;
+ *     edges         for each k, P = v_k, Q = v_((k + 1) mod 24), d = Q - P, w = X - P, L2 = d.d, t = w.d:  t <= 0: w.w <= 1;
+ *                   t >= L2: |X - Q|^2 <= 1;  else (d.x * w.y - d.y * w.x)^2 <= L2  (squared distance to the segment <= 1; P = Q too);
+ *     text          label bytes b_0 .. b_(m-1): the class's entry of labels [num_classes][24] (label_len [num_classes], 0..24),
+ *                   followed when show_scores is set by a space and the two decimal digits of min(99, (int)(score * 100.0f)) (never
+ *                   below 0; bytes past 24 are dropped).  Origin tx = xc + 3, ty = yc - 3 - 7 s, s = font_scale; with u = x - tx,
+ *                   v = y - ty the pixel is covered iff 0 <= v < 7 s, 0 <= u < 6 s m, cu = (u mod 6 s) div s < 5 and bit 4 - cu of
+ *                   font[b_j - 32][v div s] is set, j = u div 6 s.  font uint8 [95][7]: bytes 32..126, 7 rows of 5 bits, MSB
+ *                   leftmost; a byte outside 32..126 draws as '?'.
+ *   Fill coverage (only with fill_alpha > 0): the pixel is inside the integer polygon by ep24_poly24_raster's rule - in double, an
+ *     edge counts iff (y0 <= y) != (y1 <= y), crosses at x0 + ((y - y0) * (x1 - x0)) / (y1 - y0), inside iff an odd number of counting
+ *     edges have x < that crossing.
+ *   Painter's order: rows in row order (postprocess's NMS order); for each row not skipped: solid-covered -> pix = colors[cls];
+ *     else fill-covered -> per channel pix = (pix * (256 - a) + color * a + 128) >> 8, a = fill_alpha in 0..255.  A pixel that no row
+ *     covers keeps its byte (and is not written).  The result is a bit-exact function of the inputs.
+ * ------------------------------------------------------------------------------------------------ */
+#define EP24_DRAW_REC_WORDS 64        /* int32 words of one primitive record */
+#define EP24_DRAW_MAX_SIDE 16384
+#define EP24_DRAW_MAX_FONT_SCALE 1024
+/* One thread per row -> rec [n][EP24_DRAW_REC_WORDS] int32: [0] skip flag, [1] xc, [2] yc, [3..50] the 24 vertices (x, y), [51] colour
+ * (c0 | c1 << 8 | c2 << 16), [52] m, [53..58] the 24 label bytes (zero past m), [59..62] the row's pixel box (x0, y0, x1, y1, inclusive;
+ * over discs, edges and text, which also holds the fill; (0, 0, -1, -1) for a skipped row), [63] 0.  Every word of every record is
+ * written by the launch, whatever the buffer held.  colors uint8 [num_classes][3].  EP24_E_ARG: n < 0, num_classes < 1, ratio not a
+ * positive finite number, NaN conf, a null pointer with n > 0; EP24_E_UNSUPPORTED: H, W or font_scale outside their ranges. */
+int ep24_draw24_prepare(const float* det, int n, float ratio, float conf, const float* ray_cs, int H, int W, const uint8_t* colors,
+                        int num_classes, const uint8_t* labels, const int32_t* label_len, int font_scale, int show_scores,
+                        int32_t* rec, void* stream);
+/* Paints the records onto image IN PLACE: one workgroup per 64 x 16 pixel tile, every pixel read and written by exactly one thread,
+ * no atomics; the records are tested against the tile 256 at a time in row order (no cap on n), and a tile that no record's box
+ * touches writes nothing.  fill_alpha outside 0..255 is EP24_E_ARG. */
+int ep24_draw24_paint(uint8_t* image, int H, int W, const int32_t* rec, int n, const uint8_t* font, int fill_alpha, int font_scale,
+                      void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * N4  24-point label generation (yolox_24p/datasets/2+24_labels_create.py:61-116, :175-180)
  * ------------------------------------------------------------------------------------------------ */
 /* rotation_for_24p for n objects (n <= 65535 per call).  masks: uint8 instance masks (non-zero = object) somewhere in
