@@ -16,6 +16,7 @@
 //
 // Determinism: box and area are integer atomics (min, max, add) over the rows of an object - the order does not matter.
 #include "common.h"
+#include "raster_rule.h"
 
 namespace {
 
@@ -75,9 +76,9 @@ __global__ __launch_bounds__(256) void poly24_raster_kernel(const float* verts, 
         const float* v = verts + n * 48;
         const int k1 = lane == 23 ? 0 : lane + 1;
         const double x0 = v[2 * lane], y0 = v[2 * lane + 1], x1 = v[2 * k1], y1 = v[2 * k1 + 1];
-        counts = (y0 <= yc) != (y1 <= yc);
+        double xc;
+        counts = raster_edge_crossing(x0, y0, x1, y1, yc, &xc);       // the rule itself: raster_rule.h
         if (counts) {
-            const double xc = x0 + ((yc - y0) * (x1 - x0)) / (y1 - y0);
             const double cd = ceil(xc);
             c = cd > 0.0 ? (cd < (double)W ? (int)cd : W) : 0;
         }

@@ -691,8 +691,8 @@ class Engine:
             raise IndexError("ep24: the input height and width must be multiples of 32 (three stride levels), got %dx%d" % (self.IH, self.IW))
         self.images = torch.zeros(B, 3, self.IH, self.IW, dtype=torch.float32, device=self.dev)
         x2, x1, x0 = self.build_neck_inputs(neck)
-        pans = self.build_neck(neck, x2, x1, x0)
-        self.build_head(head, pans)
+        self.pans = self.build_neck(neck, x2, x1, x0)     # (pan_out2, pan_out1, pan_out0): every Act has its own buffer, so they outlive the forward (ep24.featmap)
+        self.build_head(head, self.pans)
         self._finalize()
 
     def neck_channels(self, bb):

@@ -490,11 +490,19 @@ class YOLOX(nn.Module):
             self._engines[key] = Engine(self, batch, size, dtype)
         return self._engines[key]
 
-    def forward(self, x, train=False):
+    def forward(self, x, train=False, return_fpn=False):
+        """``return_fpn=True`` (eval mode only): ``(outputs, fpn_outs)`` as the reference's yolox/models/yolox.py:49 - the three neck
+        outputs (strides 8, 16, 32) as NCHW fp32 copies; ``outputs`` is what the call without the flag returns."""
+        if return_fpn and train:
+            raise ValueError("ep24: return_fpn is an eval-mode option (model(x, train=False, return_fpn=True))")
         _lib.require_gpu()
         if not x.is_cuda:
             raise _lib.Ep24Error("ep24: input images must live on the GPU (no CPU fallback on the product path)")
         if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] % 32 or x.shape[3] % 32:
             raise IndexError("expected images [B,3,H,W] with H and W multiples of 32, got %s" % (tuple(x.shape),))
         eng = self.engine(x.shape[0], (x.shape[2], x.shape[3]), self.compute_dtype)
-        return eng.run_module_forward(x, train)
+        out = eng.run_module_forward(x, train)
+        if return_fpn:
+            from .engine import _from_act
+            return out, [_from_act(a) for a in eng.pans]
+        return out

@@ -709,6 +709,48 @@ int ep24_draw24_paint(uint8_t* image, int H, int W, const int32_t* rec, int n, c
                       void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * E4  feature-map response (csrc/featmap.hip; ep24.featmap).  The reference's title experiment
+ *     (yolox/demo_featuremap.py:330-392): the channel mean of each neck output as a heat map, and the mean of that map inside the
+ *     ground-truth region.  No allocation, no stream synchronisation, no floating-point atomics: every result is a bit-exact
+ *     function of the inputs.  All fp32 steps are separate operations (no contraction), all index arithmetic is 64-bit.
+ * ------------------------------------------------------------------------------------------------ */
+#define EP24_FEATMAP_MAX_SCALE 64
+/* out[r] = (sum of x[r * ld + c], c in [0, C)) / (float)C for M bf16 rows: a channel slice of an NHWC activation buffer with
+ * M = B * H * W (fpn_np.sum(axis=0) / fpn_channel, :345).  The sum is fp32, the division a true division.  A row's result depends on
+ * that row's C values only - not on M, the grid or its neighbours - and the summation order is a fixed function of C: G = the power
+ * of two >= C / 8 (at most 64) lanes share a row, lane g adds the values of the 16-byte chunks g, g + G, ... one by one in index order
+ * starting from 0.0f, and the G partial sums meet in a butterfly (partner distance G / 2, ..., 1).  Requirements: C % 8 == 0,
+ * C >= 8, ld % 8 == 0, ld >= C, x 16-byte aligned - anything else is EP24_E_UNSUPPORTED; M < 0, or a null pointer with M > 0, is
+ * EP24_E_ARG; M = 0 launches nothing. */
+int ep24_featmap_mean_bf16(const void* x, int64_t ld, int64_t M, int C, float* out, void* stream);
+/* range[n] = (min, max) over the `cells` values of map n (maps fp32 [N][cells]): fminf / fmaxf from (+inf, -inf), so NaNs are
+ * ignored and an empty or all-NaN map gives (+inf, -inf).  One workgroup per map.  EP24_E_ARG: N < 0, cells < 0, a null pointer. */
+int ep24_featmap_range(const float* maps, int N, int64_t cells, float* range, void* stream);
+/* Heat map: out uint8 [N][H * scale][W * scale][3], pixel (Y, X) takes cell (Y / scale, X / scale) of maps fp32 [N][H][W].  Colour
+ * index in fp32 with (lo, hi) = range[n]: t = (v - lo) / (hi - lo), q = t * 256.0f; idx = 0 if !(hi > lo) or !(q >= 0), 255 if
+ * q >= 255, else (int)q; the colour is lut[idx] of a uint8 [256][3] table.  base == NULL: the pixel is the colour.  Otherwise base is
+ * fp32 [N][3][H * scale][W * scale] (the network input: planar, 0 - 255), its byte is 0 if !(b >= 0), 255 if b >= 255, else (int)b,
+ * and per channel out = (byte * (256 - alpha) + colour * alpha + 128) >> 8 - the fill expression of ep24_draw24_paint.  Plane ch of
+ * base, column ch of lut and channel ch of out belong together.  Every byte of out is written.  EP24_E_ARG: N < 0, alpha outside
+ * 0..255, a null maps / range / lut / out with N > 0; EP24_E_UNSUPPORTED: scale outside 1..EP24_FEATMAP_MAX_SCALE, H or W < 1, or
+ * an output side above EP24_DRAW_MAX_SIDE. */
+int ep24_featmap_render(const float* maps, int N, int H, int W, int scale, const float* range, const uint8_t* lut, const float* base,
+                        int alpha, uint8_t* out, void* stream);
+/* Response of maps fp32 [B][H][W] inside the regions of labels fp32 [B][L][51] (class, centre, 24 x (x, y) in pixels of the network
+ * input): sum[b][l] = the double-precision sum of the region's cells (a fixed order), count[b][l] their number, mean = sum / count,
+ * or 0 with count 0.  A row whose 51 values, added in fp32 in index order, do not come to more than 0 is padding; a row with a
+ * non-finite vertex, or one of magnitude >= 2^20, has an empty region: count, sum and mean are 0 for both.
+ *   mode 0 "rect" (:378-385): the bounding rectangle of the 24 vertices; s = (float)stride, x0 = (int)(xmin / s), x1 = (int)(xmax / s),
+ *     the same in y (fp32, truncation toward zero); the edges are clamped to [0, W] / [0, H] (the reference's slice would wrap a
+ *     negative index) and the region is the half-open [y0, y1) x [x0, x1).
+ *   mode 1 "poly24": cell (i, j) belongs iff the point ((j + 0.5) * stride, (i + 0.5) * stride) - the anchor centre of
+ *     get_in_boxes_info - is inside the 24-gon by ep24_poly24_raster's crossing rule in double (csrc/raster_rule.h).
+ * One workgroup per (image, row).  EP24_E_ARG: B or L < 0, stride < 1, another mode, a null pointer with B * L > 0;
+ * EP24_E_UNSUPPORTED: H or W outside 1..EP24_DRAW_MAX_SIDE. */
+int ep24_featmap_response(const float* maps, int B, int H, int W, int stride, const float* labels, int L, int mode, double* sum,
+                          int32_t* count, double* mean, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * N4  24-point label generation (yolox_24p/datasets/2+24_labels_create.py:61-116, :175-180)
  * ------------------------------------------------------------------------------------------------ */
 /* rotation_for_24p for n objects (n <= 65535 per call).  masks: uint8 instance masks (non-zero = object) somewhere in
