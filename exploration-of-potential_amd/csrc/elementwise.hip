@@ -1121,22 +1121,44 @@ __device__ __forceinline__ float ema_step(float e, float pnew, float d, float om
 // a padded Cin row).  The step used to start with pack_batched_kernel re-reading all 217 MB of masters on the main lane (98 us on
 // the critical path of YOLOX-l, profiles/r04_step_timeline.csv); now the freshly written values leave as 8-byte bf16 stores from
 // the pass that has them in registers.  base = index of p[0] in the whole flat buffer (the range form passes p + first).
+//
+// Weight decay by parameter group (DECAY): `decay_grp[(base + i) >> 6]` != 0 marks a 64-element group whose elements decay - the
+// conv weights, stock YOLOX's pg1; BatchNorm vectors and biases do not.  For those the scaled gradient becomes g*s + decay*p (two
+// more roundings, decay = hp[5] in the device-block form) before it enters the momentum, torch.optim.SGD's weight_decay; every other
+// element takes the very operations of the plain form.  A template flag, and the two extra arguments (decay, decay_grp) as a trailing
+// pack that is empty without it: sgd_kernel<false> keeps the kernel arguments and, instruction for instruction, the code the kernel
+// had before the flag (a wrapper around a shared body did not: other address arithmetic, other registers).  The table costs one
+// byte per 256 bytes of p.
 constexpr int WF_NONE = -2147483647 - 1;
+struct DecayArgs { float decay; const uint8_t* grp; };
+template <bool DECAY, typename... X>
 __global__ __launch_bounds__(256) void sgd_kernel(float* p, const float* g, float* buf, long n, float lr, float mom,
                                                   float gscale, const int* first_flag, const float* hp, float* ema,
-                                                  long base = 0, const int* wf_delta = nullptr, bf16* wf = nullptr) {
+                                                  long base, const int* wf_delta, bf16* wf, X... x) {
+    float decay = 0.f;
+    const uint8_t* decay_grp = nullptr;
+    if constexpr (DECAY) {
+        const DecayArgs t{x...};
+        decay = t.decay;
+        decay_grp = t.grp;
+    }
     const int first = *first_flag;
     float d = 0.f, omd = 0.f;
-    if (hp) { lr = hp[0]; mom = hp[1]; gscale = hp[2]; d = hp[3]; omd = hp[4]; }
+    if (hp) {
+        lr = hp[0]; mom = hp[1]; gscale = hp[2]; d = hp[3]; omd = hp[4];
+        if (DECAY) decay = hp[5];
+    }
     for (long i = ((long)blockIdx.x * 256 + threadIdx.x) * 4; i < n; i += (long)gridDim.x * 1024) {
         if (i + 3 < n) {
             f32x4 gv = *reinterpret_cast<const f32x4*>(g + i);
             f32x4 pv = *reinterpret_cast<const f32x4*>(p + i);
             f32x4 bv = first ? (f32x4){0.f, 0.f, 0.f, 0.f} : *reinterpret_cast<const f32x4*>(buf + i);
             const int wd = wf_delta ? wf_delta[(base + i) >> 6] : WF_NONE;
+            const bool dec = DECAY && decay_grp[(base + i) >> 6] != 0;      // base and i are multiples of 4: one group per vector
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                const float gg = gv[j] * gscale;
+                float gg = gv[j] * gscale;
+                if (DECAY) gg = dec ? gg + decay * pv[j] : gg;
                 bv[j] = first ? gg : mom * bv[j] + gg;
                 pv[j] -= lr * (gg + mom * bv[j]);
             }
@@ -1156,7 +1178,8 @@ __global__ __launch_bounds__(256) void sgd_kernel(float* p, const float* g, floa
             }
         } else {
             for (long k = i; k < n; ++k) {
-                const float gg = g[k] * gscale;
+                float gg = g[k] * gscale;
+                if (DECAY) gg = decay_grp[(base + k) >> 6] != 0 ? gg + decay * p[k] : gg;
                 const float b = first ? gg : mom * buf[k] + gg;
                 buf[k] = b;
                 p[k] -= lr * (gg + mom * b);
@@ -1175,6 +1198,9 @@ __global__ __launch_bounds__(256) void ema_kernel(float* ema, const float* src, 
 
 __global__ void set_hparams_kernel(float* hp, float lr, float mom, float gscale, float d, float omd) {
     hp[0] = lr; hp[1] = mom; hp[2] = gscale; hp[3] = d; hp[4] = omd;
+}
+__global__ void set_hparams_decay_kernel(float* hp, float lr, float mom, float gscale, float d, float omd, float decay) {
+    hp[0] = lr; hp[1] = mom; hp[2] = gscale; hp[3] = d; hp[4] = omd; hp[5] = decay;
 }
 __global__ void clear_flag_kernel(int* f) { *f = 0; }
 
@@ -1439,8 +1465,8 @@ extern "C" int ep24_sgd_nesterov(float* p, const float* g, float* buf, int64_t n
                                  int32_t* first_flag, void* stream) {
     EP24_REQUIRE(p && g && buf && first_flag && n > 0, EP24_E_ARG, "sgd_nesterov: bad arguments");
     EP24_REQUIRE(((uintptr_t)p | (uintptr_t)g | (uintptr_t)buf) % 16 == 0, EP24_E_ARG, "sgd_nesterov: 16-byte alignment");
-    hipLaunchKernelGGL(sgd_kernel, dim3(cap_grid((n + 3) / 4)), dim3(256), 0, S_, p, g, buf, n, lr, momentum, grad_scale, first_flag,
-                       (const float*)nullptr, (float*)nullptr);
+    hipLaunchKernelGGL(sgd_kernel<false>, dim3(cap_grid((n + 3) / 4)), dim3(256), 0, S_, p, g, buf, n, lr, momentum, grad_scale, first_flag,
+                       (const float*)nullptr, (float*)nullptr, 0L, (const int*)nullptr, (bf16*)nullptr);
     hipLaunchKernelGGL(clear_flag_kernel, dim3(1), dim3(1), 0, S_, first_flag);
     EP24_LAUNCH_CHECK("ep24_sgd_nesterov");
     return EP24_OK;
@@ -1450,7 +1476,8 @@ extern "C" int ep24_sgd_nesterov_hp(float* p, const float* g, float* buf, int64_
                                     float* ema, void* stream) {
     EP24_REQUIRE(p && g && buf && hp && first_flag && n > 0, EP24_E_ARG, "sgd_nesterov_hp: bad arguments");
     EP24_REQUIRE(((uintptr_t)p | (uintptr_t)g | (uintptr_t)buf | (uintptr_t)ema) % 16 == 0, EP24_E_ARG, "sgd_nesterov_hp: 16-byte alignment");
-    hipLaunchKernelGGL(sgd_kernel, dim3(cap_grid((n + 3) / 4)), dim3(256), 0, S_, p, g, buf, n, 0.f, 0.f, 0.f, first_flag, hp, ema);
+    hipLaunchKernelGGL(sgd_kernel<false>, dim3(cap_grid((n + 3) / 4)), dim3(256), 0, S_, p, g, buf, n, 0.f, 0.f, 0.f, first_flag, hp, ema,
+                       0L, (const int*)nullptr, (bf16*)nullptr);
     hipLaunchKernelGGL(clear_flag_kernel, dim3(1), dim3(1), 0, S_, first_flag);
     EP24_LAUNCH_CHECK("ep24_sgd_nesterov_hp");
     return EP24_OK;
@@ -1463,8 +1490,8 @@ extern "C" int ep24_sgd_nesterov_hp_range(float* p, const float* g, float* buf, 
                                           int32_t* first_flag, float* ema, int last, void* stream) {
     EP24_REQUIRE(p && g && buf && hp && first_flag && n > 0 && first >= 0 && first % 4 == 0, EP24_E_ARG, "sgd_nesterov_hp_range: bad arguments");
     EP24_REQUIRE(((uintptr_t)p | (uintptr_t)g | (uintptr_t)buf | (uintptr_t)ema) % 16 == 0, EP24_E_ARG, "sgd_nesterov_hp_range: 16-byte alignment");
-    hipLaunchKernelGGL(sgd_kernel, dim3(cap_grid((n + 3) / 4)), dim3(256), 0, S_, p + first, g + first, buf + first, n, 0.f, 0.f, 0.f, first_flag, hp,
-                       ema ? ema + first : nullptr);
+    hipLaunchKernelGGL(sgd_kernel<false>, dim3(cap_grid((n + 3) / 4)), dim3(256), 0, S_, p + first, g + first, buf + first, n, 0.f, 0.f, 0.f, first_flag, hp,
+                       ema ? ema + first : nullptr, 0L, (const int*)nullptr, (bf16*)nullptr);
     if (last) hipLaunchKernelGGL(clear_flag_kernel, dim3(1), dim3(1), 0, S_, first_flag);
     EP24_LAUNCH_CHECK("ep24_sgd_nesterov_hp_range");
     return EP24_OK;
@@ -1478,10 +1505,39 @@ extern "C" int ep24_sgd_nesterov_hp_range_pack(float* p, const float* g, float* 
                  "sgd_nesterov_hp_range_pack: bad arguments");
     EP24_REQUIRE(((uintptr_t)p | (uintptr_t)g | (uintptr_t)buf | (uintptr_t)ema) % 16 == 0 && (uintptr_t)wf % 16 == 0, EP24_E_ARG,
                  "sgd_nesterov_hp_range_pack: 16-byte alignment");
-    hipLaunchKernelGGL(sgd_kernel, dim3(cap_grid((n + 3) / 4)), dim3(256), 0, S_, p + first, g + first, buf + first, n, 0.f, 0.f, 0.f, first_flag, hp,
+    hipLaunchKernelGGL(sgd_kernel<false>, dim3(cap_grid((n + 3) / 4)), dim3(256), 0, S_, p + first, g + first, buf + first, n, 0.f, 0.f, 0.f, first_flag, hp,
                        ema ? ema + first : nullptr, (long)first, (const int*)wf_delta, (bf16*)wf);
     if (last) hipLaunchKernelGGL(clear_flag_kernel, dim3(1), dim3(1), 0, S_, first_flag);
     EP24_LAUNCH_CHECK("ep24_sgd_nesterov_hp_range_pack");
+    return EP24_OK;
+}
+
+// Weight decay by parameter group (sgd_kernel<true>): the by-value form over a whole buffer ...
+extern "C" int ep24_sgd_nesterov_decay(float* p, const float* g, float* buf, int64_t n, float lr, float momentum, float grad_scale,
+                                       float weight_decay, const uint8_t* decay_grp, int32_t* first_flag, void* stream) {
+    EP24_REQUIRE(p && g && buf && decay_grp && first_flag && n > 0, EP24_E_ARG, "sgd_nesterov_decay: bad arguments");
+    EP24_REQUIRE(((uintptr_t)p | (uintptr_t)g | (uintptr_t)buf) % 16 == 0, EP24_E_ARG, "sgd_nesterov_decay: 16-byte alignment");
+    hipLaunchKernelGGL((sgd_kernel<true, float, const uint8_t*>), dim3(cap_grid((n + 3) / 4)), dim3(256), 0, S_, p, g, buf, n, lr, momentum,
+                       grad_scale, first_flag, (const float*)nullptr, (float*)nullptr, 0L, (const int*)nullptr, (bf16*)nullptr, weight_decay, decay_grp);
+    hipLaunchKernelGGL(clear_flag_kernel, dim3(1), dim3(1), 0, S_, first_flag);
+    EP24_LAUNCH_CHECK("ep24_sgd_nesterov_decay");
+    return EP24_OK;
+}
+
+// ... and the device-block form on elements [first, first + n), decay = hp[5]; ema and wf_delta / wf (both or neither) are nullable, so
+// this one entry point stands for the _hp, _hp_range and _hp_range_pack forms.  decay_grp, like wf_delta, covers the WHOLE flat buffer.
+extern "C" int ep24_sgd_nesterov_decay_hp_range_pack(float* p, const float* g, float* buf, int64_t first, int64_t n, const float* hp,
+                                                     int32_t* first_flag, float* ema, int last, const int32_t* wf_delta, void* wf,
+                                                     const uint8_t* decay_grp, void* stream) {
+    EP24_REQUIRE(p && g && buf && hp && first_flag && decay_grp && (wf_delta != nullptr) == (wf != nullptr) && n > 0 && first >= 0 &&
+                     first % 4 == 0,
+                 EP24_E_ARG, "sgd_nesterov_decay_hp_range_pack: bad arguments");
+    EP24_REQUIRE(((uintptr_t)p | (uintptr_t)g | (uintptr_t)buf | (uintptr_t)ema) % 16 == 0 && (uintptr_t)wf % 16 == 0, EP24_E_ARG,
+                 "sgd_nesterov_decay_hp_range_pack: 16-byte alignment");
+    hipLaunchKernelGGL((sgd_kernel<true, float, const uint8_t*>), dim3(cap_grid((n + 3) / 4)), dim3(256), 0, S_, p + first, g + first, buf + first, n,
+                       0.f, 0.f, 0.f, first_flag, hp, ema ? ema + first : nullptr, (long)first, (const int*)wf_delta, (bf16*)wf, 0.f, decay_grp);
+    if (last) hipLaunchKernelGGL(clear_flag_kernel, dim3(1), dim3(1), 0, S_, first_flag);
+    EP24_LAUNCH_CHECK("ep24_sgd_nesterov_decay_hp_range_pack");
     return EP24_OK;
 }
 
@@ -1498,6 +1554,15 @@ extern "C" int ep24_set_hparams(float* hp, float lr, float momentum, float grad_
     EP24_REQUIRE(hp, EP24_E_ARG, "set_hparams: null pointer");
     hipLaunchKernelGGL(set_hparams_kernel, dim3(1), dim3(1), 0, S_, hp, lr, momentum, grad_scale, ema_decay, one_minus_decay);
     EP24_LAUNCH_CHECK("ep24_set_hparams");
+    return EP24_OK;
+}
+
+extern "C" int ep24_set_hparams_decay(float* hp, float lr, float momentum, float grad_scale, float ema_decay, float one_minus_decay,
+                                      float weight_decay, void* stream) {
+    EP24_REQUIRE(hp, EP24_E_ARG, "set_hparams_decay: null pointer");
+    hipLaunchKernelGGL(set_hparams_decay_kernel, dim3(1), dim3(1), 0, S_, hp, lr, momentum, grad_scale, ema_decay, one_minus_decay,
+                       weight_decay);
+    EP24_LAUNCH_CHECK("ep24_set_hparams_decay");
     return EP24_OK;
 }
 

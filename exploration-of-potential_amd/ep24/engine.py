@@ -190,6 +190,7 @@ class ParamHome:
                 self._add(VecSeg([bn_.bias]))
             elif isinstance(mod, tuple) and mod[0] == "unused":      # in the state dict, not in the graph: gradient stays 0
                 self._add(VecSeg([mod[1]]))
+                self.order[-1].unused = True                         # never decays either: torch skips a parameter without a gradient
             elif isinstance(mod, tuple) and mod[0] in ("csp_merged", "pair_merged"):
                 # two BaseConv units over the same input as one GEMM + one BN launch; (first, second) = channel order of the output
                 c2, c1 = (mod[1].conv2, mod[1].conv1) if mod[0] == "csp_merged" else (mod[1], mod[2])
@@ -260,6 +261,12 @@ class ParamHome:
                 self.pack_rest.append(seg)
         self.wf_delta = delta.to(dev)
         self.wf_current = False
+        # Weight decay by parameter group (csrc/elementwise.hip sgd_kernel<true>): one byte per 64 flat elements, next to wf_delta; non-zero =
+        # the group decays.  Default: the conv segments, which for every supported model are stock YOLOX's pg1 (every .weight that is
+        # not a BatchNorm's: convs, predictors, depthwise, swapped-backbone convs); vectors (BatchNorm weights and biases, predictor
+        # biases, unused parameters) never decay.  A segment's alignment padding belongs to its group: zeros, which decay to zeros.
+        self.decay_grp = torch.zeros(max(n // 64, 1), dtype=torch.uint8, device=dev)
+        self.set_decay_params([p for seg in self.convs for p in seg.params])
         self._rest_tables = None
         if self.pack_rest:                                # descriptor tables of the packing kernel for just those segments (built now:
             rows, pref, tpref = [], [0], [0]              # the call sits inside captured graphs)
@@ -370,19 +377,45 @@ class ParamHome:
     def zero_grad(self):
         call("memset_zero", ptr(self.gflat), self.numel * 4, stream_ptr())
 
-    def sgd(self, lr, momentum, grad_scale=1.0):
+    def set_decay_params(self, params):
+        """The parameters that weight decay applies to (default: those of the conv segments).  A segment decays as a whole - its
+        64-element groups carry one flag - so parameters that share one (merged CSP pairs, the reg + obj predictors) must agree."""
+        want = {id(p) for p in params}
+        unknown = want - {id(p) for p in self.by_param}
+        if unknown:
+            raise _lib.Ep24Error("ep24: set_decay_params: %d parameter(s) that are not this model's" % len(unknown))
+        table = torch.zeros(self.decay_grp.numel(), dtype=torch.uint8)
+        for seg in self.order:
+            flags = {id(p) in want for p in seg.params}
+            if len(flags) > 1:
+                raise _lib.Ep24Error("ep24: set_decay_params: the %d parameters of the segment at element %d share one launch and one "
+                                     "decay flag, but only some of them are in the decaying set" % (len(seg.params), seg.off))
+            if flags == {True}:
+                table[seg.off // 64:(seg.off + seg.numel + 63) // 64] = 1
+        self.decay_grp.copy_(table)
+
+    def sgd(self, lr, momentum, grad_scale=1.0, weight_decay=0.0):
+        if weight_decay:
+            call("sgd_nesterov_decay", ptr(self.flat), ptr(self.gflat), ptr(self.mflat), self.numel, float(lr), float(momentum),
+                 float(grad_scale), float(weight_decay), ptr(self.decay_grp), ptr(self.first_flag), stream_ptr())
+            return
         call("sgd_nesterov", ptr(self.flat), ptr(self.gflat), ptr(self.mflat), self.numel, float(lr), float(momentum),
              float(grad_scale), ptr(self.first_flag), stream_ptr())
 
-    def sgd_hp(self, hp, ema_home=None, lo=0, hi=None, last=True):
+    def sgd_hp(self, hp, ema_home=None, lo=0, hi=None, last=True, decay=False):
         """The same update with lr / momentum / grad_scale (and the EMA decay) read from the device block ``hp``; with
         ``ema_home`` the EMA copy of the parameters and of the BatchNorm running statistics is advanced as well.
         ``lo`` / ``hi``: only elements [lo, hi) of the flat buffers (ep24.train updates the parameters whose gradients are
-        complete while backward still runs); ``last``: this call finishes the step."""
+        complete while backward still runs); ``last``: this call finishes the step.  ``decay``: the groups of ``decay_grp`` decay by
+        ``hp[5]`` (ep24_set_hparams_decay); without it the call is the one it has always been."""
         if ema_home is not None and (ema_home.numel, ema_home.bnumel) != (self.numel, self.bnumel):
             raise _lib.Ep24Error("ep24: the EMA model's parameter layout differs from the trained model's")
         hi = self.numel if hi is None else hi
-        if hi > lo:
+        if hi > lo and decay:
+            call("sgd_nesterov_decay_hp_range_pack", ptr(self.flat), ptr(self.gflat), ptr(self.mflat), lo, hi - lo, ptr(hp),
+                 ptr(self.first_flag), ptr(ema_home.flat) if ema_home is not None else None, 1 if last else 0, ptr(self.wf_delta),
+                 ptr(self.wf), ptr(self.decay_grp), stream_ptr())
+        elif hi > lo:
             call("sgd_nesterov_hp_range_pack", ptr(self.flat), ptr(self.gflat), ptr(self.mflat), lo, hi - lo, ptr(hp), ptr(self.first_flag),
                  ptr(ema_home.flat) if ema_home is not None else None, 1 if last else 0, ptr(self.wf_delta), ptr(self.wf), stream_ptr())
         if last and ema_home is not None and self.bnumel:

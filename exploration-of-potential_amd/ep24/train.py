@@ -12,15 +12,60 @@ from . import _lib, loss as eloss
 from .engine import param_home
 
 
-class SGD(torch.optim.Optimizer):
-    """``torch.optim.SGD(params, lr, momentum, nesterov=True)`` semantics (yolox_24p/exp/yolox_base.py:120-124,
-    no weight decay) as ONE fused kernel over the model's flat parameter / gradient / momentum buffers."""
+def yolox_param_groups(model, weight_decay):
+    """Stock YOLOX's three optimizer groups in its order (yolox/exp/yolox_base.py:205-221): the weights of every BatchNorm2d and of
+    every module with "bn" in its name (no decay), every other module's ``.weight`` (``weight_decay``), every ``.bias`` (no decay)."""
+    norm, decayed, biases = [], [], []
+    for name, mod in model.named_modules():
+        w, b = getattr(mod, "weight", None), getattr(mod, "bias", None)
+        if isinstance(b, torch.nn.Parameter):
+            biases.append(b)
+        if not isinstance(w, torch.nn.Parameter):
+            continue
+        (norm if isinstance(mod, torch.nn.BatchNorm2d) or "bn" in name else decayed).append(w)
+    return [{"params": norm, "weight_decay": 0.0}, {"params": decayed, "weight_decay": float(weight_decay)},
+            {"params": biases, "weight_decay": 0.0}]
 
-    def __init__(self, params, lr, momentum=0.9, nesterov=True, model=None):
+
+class SGD(torch.optim.Optimizer):
+    """``torch.optim.SGD(params, lr, momentum, nesterov=True, weight_decay)`` semantics as ONE fused kernel over the model's flat
+    parameter / gradient / momentum buffers.  Without weight decay - the default - it is the 24-point trainer's optimizer
+    (yolox_24p/exp/yolox_base.py:120-124).  ``params`` is a flat list (with ``weight_decay`` for all of it) or a list of group dicts
+    such as ``yolox_param_groups``: every group's decay is 0 or one common value w, the parameters of the groups with w become the
+    home's decaying set (``ParamHome.set_decay_params``; parameters that never receive a gradient stay out of it, as in torch), and
+    the groups share one lr and one momentum."""
+
+    def __init__(self, params, lr, momentum=0.9, nesterov=True, model=None, weight_decay=0.0):
         if not nesterov or model is None:
             raise NotImplementedError("ep24.SGD implements the reference's nesterov SGD over an ep24 model")
-        super().__init__(list(params), dict(lr=lr, momentum=momentum, nesterov=True))
+        super().__init__(list(params), dict(lr=lr, momentum=momentum, nesterov=True, weight_decay=float(weight_decay)))
         self.model = model
+        self._installed = None
+        _ = self.weight_decay                             # refuses what the kernel cannot do before anything else happens
+        if next(model.parameters()).is_cuda:
+            self._install_decay()
+
+    @property
+    def weight_decay(self):
+        """The one non-zero decay of the groups, or 0.0."""
+        vals = sorted({float(g.get("weight_decay", 0.0)) for g in self.param_groups})
+        if vals and vals[0] < 0:
+            raise ValueError("ep24.SGD: negative weight_decay %r" % vals[0])
+        nz = [v for v in vals if v != 0.0]
+        if len(nz) > 1:
+            raise NotImplementedError("ep24.SGD: the fused update carries ONE weight decay (a group decays by it or not at all); "
+                                      "the groups ask for %s" % nz)
+        return nz[0] if nz else 0.0
+
+    def _install_decay(self):
+        """The groups with a non-zero decay -> the home's table.  Nothing is touched while no group decays."""
+        which = tuple(float(g.get("weight_decay", 0.0)) != 0.0 for g in self.param_groups)
+        if which == self._installed or (self._installed is None and not any(which)):
+            return
+        home = param_home(self.model)
+        home.set_decay_params([p for g, on in zip(self.param_groups, which) if on for p in g["params"]
+                               if not getattr(home.by_param[p], "unused", False)])
+        self._installed = which
 
     def zero_grad(self, set_to_none=False):
         home = param_home(self.model)
@@ -30,7 +75,13 @@ class SGD(torch.optim.Optimizer):
     @torch.no_grad()
     def step(self, closure=None, grad_scale=1.0):
         g = self.param_groups[0]
-        param_home(self.model).sgd(g["lr"], g["momentum"], grad_scale)
+        for other in self.param_groups[1:]:
+            if (other["lr"], other["momentum"]) != (g["lr"], g["momentum"]):
+                raise ValueError("ep24.SGD: one lr and one momentum for all groups (the update is one launch); got lr %s, momentum %s"
+                                 % ([x["lr"] for x in self.param_groups], [x["momentum"] for x in self.param_groups]))
+        w = self.weight_decay
+        self._install_decay()
+        param_home(self.model).sgd(g["lr"], g["momentum"], grad_scale, w)
 
     def state_dict(self):
         home = param_home(self.model)
@@ -41,6 +92,10 @@ class SGD(torch.optim.Optimizer):
         return sd
 
     def load_state_dict(self, sd):
+        have, got = [len(g["params"]) for g in self.param_groups], [len(g["params"]) for g in sd["param_groups"]]
+        if have != got:                                   # indices of another layout would scatter momentum into the wrong parameters
+            raise ValueError("ep24.SGD: loaded state dict contains parameter groups of sizes %s that do not match the sizes of the "
+                             "optimizer's groups %s (a checkpoint written with another --weight-decay setting?)" % (got, have))
         home = param_home(self.model)
         order = [p for grp in self.param_groups for p in grp["params"]]
         for i, st in sd.get("state", {}).items():
@@ -49,6 +104,9 @@ class SGD(torch.optim.Optimizer):
                 home.first_flag.zero_()
         for grp, new in zip(self.param_groups, sd["param_groups"]):
             grp["lr"], grp["momentum"] = new["lr"], new["momentum"]
+            grp["weight_decay"] = float(new.get("weight_decay", 0.0))
+        _ = self.weight_decay
+        self._install_decay()
 
 
 class TrainStep:
@@ -61,7 +119,7 @@ class TrainStep:
     """
 
     def __init__(self, model, loss_fn, lr, momentum=0.9, batch=None, size=640, reducer=None, use_graph=True,
-                 graph_backward=True, ema=None, use_l1=False):
+                 graph_backward=True, ema=None, use_l1=False, weight_decay=0.0):
         _lib.require_gpu()
         self.model, self.loss_fn = model, loss_fn
         self.eng = model.engine(batch, size)
@@ -74,6 +132,11 @@ class TrainStep:
         self.ema_home = ema.homes(model)[1] if ema is not None else None
         self.hp = torch.zeros(8, dtype=torch.float32, device=self.eng.dev)
         self._hp_dirty = True
+        # weight decay of the home's decaying groups (ParamHome.decay_grp: the conv weights unless ep24.train.SGD or the caller
+        # installed another set): hp[5].  0 keeps the launches - and the captured graphs - of a step without decay
+        if weight_decay < 0:
+            raise ValueError("TrainStep: negative weight_decay %r" % weight_decay)
+        self.weight_decay = float(weight_decay)
         self.use_l1 = False
         eng = self.eng
         self.ws = loss_fn.workspace(eng.B, eng.A, eng.dev)
@@ -105,6 +168,19 @@ class TrainStep:
             self.lr = lr
             self._hp_dirty = True
 
+    def set_weight_decay(self, w):
+        """Weight decay of the following steps.  Between two non-zero values only hp[5] changes; switching it on or off changes
+        which kernel the update launches, so the graphs are captured again on the next step (like ``set_use_l1``)."""
+        w = float(w)
+        if w < 0:
+            raise ValueError("TrainStep: negative weight_decay %r" % w)
+        if w == self.weight_decay:
+            return
+        if (w != 0.0) != (self.weight_decay != 0.0):
+            self.graphs = None
+        self.weight_decay = w
+        self._hp_dirty = True
+
     def set_use_l1(self, on):
         """The reference's ``use_l1`` switch on head and loss (yolo_head_24p.py:128, losses.py:163; its yolox ancestor
         turns it on for the last no-aug epochs).  The L1 buffers become launch arguments, so the graphs are captured
@@ -122,8 +198,12 @@ class TrainStep:
     def _push_hparams(self):
         d, omd = self.ema.next_decay() if self.ema is not None else (0.0, 0.0)
         if self._hp_dirty or self.ema is not None:
-            _lib.call("set_hparams", _lib.ptr(self.hp), float(self.lr), float(self.momentum), 1.0 / self.world, float(d),
-                      float(omd), _lib.stream_ptr())
+            if self.weight_decay:
+                _lib.call("set_hparams_decay", _lib.ptr(self.hp), float(self.lr), float(self.momentum), 1.0 / self.world, float(d),
+                          float(omd), self.weight_decay, _lib.stream_ptr())
+            else:
+                _lib.call("set_hparams", _lib.ptr(self.hp), float(self.lr), float(self.momentum), 1.0 / self.world, float(d),
+                          float(omd), _lib.stream_ptr())
             self._hp_dirty = False
 
     # the three phases, each a pure launch sequence on the current stream
@@ -204,7 +284,7 @@ class TrainStep:
         eng._run(eng.bwd[lo:hi])
 
     def _phase_update(self, lo=0, hi=None, last=True):
-        self.home.sgd_hp(self.hp, self.ema_home, lo, hi, last)
+        self.home.sgd_hp(self.hp, self.ema_home, lo, hi, last, decay=self.weight_decay != 0.0)
 
     def _early_update_cut(self, segs):
         """Where the flat parameter buffer is cut for the two-part update.  The buffer is in execution order, so backward completes it

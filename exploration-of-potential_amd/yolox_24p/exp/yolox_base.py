@@ -121,10 +121,15 @@ class Exp(BaseExp):
             targets[..., 2::2] = targets[..., 2::2] * scale_y
         return inputs, targets
 
-    def get_optimizer(self, lr):
-        """Takes the learning rate (not the batch size), like the 24p trainer (yolox_base.py:120-124)."""
-        from ep24.train import SGD
-        self.optimizer = SGD(self.model.parameters(), lr=lr, momentum=self.momentum, nesterov=True, model=self.model)
+    def get_optimizer(self, lr, weight_decay=None):
+        """Takes the learning rate (not the batch size), like the 24p trainer (yolox_base.py:120-124).  ``weight_decay`` None or 0:
+        that trainer's optimizer, one group without decay (the default).  A positive value: stock YOLOX's three groups
+        (``ep24.train.yolox_param_groups``: BatchNorm weights / every other weight, decayed / biases), in the same fused update."""
+        from ep24.train import SGD, yolox_param_groups
+        if weight_decay:
+            self.optimizer = SGD(yolox_param_groups(self.model, weight_decay), lr=lr, momentum=self.momentum, nesterov=True, model=self.model)
+        else:
+            self.optimizer = SGD(self.model.parameters(), lr=lr, momentum=self.momentum, nesterov=True, model=self.model)
         return self.optimizer
 
     def get_lr_scheduler(self, lr, iters_per_epoch, **kwargs):

@@ -15,6 +15,8 @@ The reference carries three more pieces that its 24p trainer never switches on (
 here and all of them run inside the captured step: ``--sched`` follows ``exp.get_lr_scheduler`` (yoloxwarmcos,
 exp/yolox_base.py:155-167) per iteration, ``--ema`` keeps a ``ModelEMA`` copy (utils/ema.py) that is saved with the
 checkpoint, ``--l1`` turns ``use_l1`` on for head and loss from epoch ``exp.L1_epoch`` on (exp/yolox_base.py:38).
+``--weight-decay [W]`` is the fourth piece of that recipe: stock YOLOX's three optimizer groups (yolox/exp/yolox_base.py:198-224),
+``exp.weight_decay`` (or W) on every weight that is not a BatchNorm's, applied by the fused update itself.
 """
 import argparse
 import os
@@ -92,7 +94,7 @@ class Trainer:
         model = exp.get_model()
         model.to(self.device)
         self.model = model
-        self.optimizer = exp.get_optimizer(args.learn_rate)
+        self.optimizer = exp.get_optimizer(args.learn_rate, weight_decay_arg(args, exp))
         self.max_iter = len(self.train_loader)
         # -c / --resume / -e: the reference's parser accepts them and its trainer never reads them (train_24p.py:180-211); here
         # they load what save_ckpt wrote.  The checkpoint goes in AFTER get_model() (which re-applies the bias prior on every
@@ -133,8 +135,9 @@ class Trainer:
                 self.ema_model.updates = int(ck.get("ema_updates", 0))
         step_fn = None
         if not args.no_graph:
+            # the optimizer's decay, not the flag's: --resume has restored the checkpoint's value by now
             step_fn = TrainStep(model, self.loss_func, lr=args.learn_rate, momentum=exp.momentum, batch=args.batch_size,
-                                size=tuple(self.input_size), reducer=reducer, ema=self.ema_model)
+                                size=tuple(self.input_size), reducer=reducer, ema=self.ema_model, weight_decay=self.optimizer.weight_decay)
         print("Training start... (rank %d/%d, %s)" % (self.rank, self.world, "captured step" if step_fn else "eager API"))
         done = False
         self.epoch = self.start_epoch
@@ -369,6 +372,18 @@ class Trainer:
         save_checkpoint(state, update_best_ckpt, self.file_name, ckpt_name)
 
 
+def weight_decay_arg(args, exp):
+    """--weight-decay absent: None (one optimizer group, no decay - the 24-point trainer's optimizer); the bare flag: the Exp's
+    ``weight_decay``; with a value: that value."""
+    w = getattr(args, "weight_decay", None)
+    if w is None:
+        return None
+    w = float(exp.weight_decay if w is EXP_VALUE else w)
+    if w < 0:
+        raise SystemExit("train_24p.py: --weight-decay %r is negative" % w)
+    return w
+
+
 def check_mixup_args(args):
     """--mixup blends a second image into the mosaic images of --augment: it needs --augment."""
     if getattr(args, "mixup", False) and not args.augment:
@@ -384,6 +399,9 @@ def check_fisheye_args(args):
         raise SystemExit("train_24p.py: --fisheye-theta works on the raw uint8 batches behind the prefetcher (drop --no-prefetch / --fp32-batches)")
     if not 15 <= lo <= hi <= 180:
         raise SystemExit("train_24p.py: --fisheye-theta LO HI needs 15 <= LO <= HI <= 180")
+
+
+EXP_VALUE = object()       # --weight-decay without a value (not a string: argparse would hand it to float())
 
 
 def make_parser():
@@ -408,6 +426,9 @@ def make_parser():
     p.add_argument("--sched", action="store_true", help="follow exp.get_lr_scheduler (yoloxwarmcos) instead of a constant rate")
     p.add_argument("--ema", action="store_true", help="keep a ModelEMA copy of the model (saved as ema_model)")
     p.add_argument("--l1", action="store_true", help="switch use_l1 on from epoch exp.L1_epoch")
+    p.add_argument("--weight-decay", default=None, type=float, nargs="?", const=EXP_VALUE, metavar="W", help="stock YOLOX's optimizer "
+                   "groups: weight decay W (without a value: exp.weight_decay) on every weight that is not a BatchNorm's, none on "
+                   "BatchNorm weights and biases; saved with the optimizer state and restored by --resume (default: no decay)")
     p.add_argument("--prefetch", action="store_true", help="(default since round 4; kept for old command lines) upload the next batch on a side stream: ep24.input.DataPrefetcher")
     p.add_argument("--loader-workers", default=None, type=int, help="processes of the synthetic loader (default: the Exp's loader_workers)")
     p.add_argument("--loader-pin", default=None, type=int, choices=(0, 1), help="page-locked batches from the loader (default: with loader processes and fp32 batches)")

@@ -457,7 +457,8 @@ int ep24_circle_lens(const float* gt_cx, const float* gt_cy, const float* gt_r, 
                      const float* pd_r, float* res_inter, float* dist, int G, int P, int pairwise, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
- * a11  optimizer (yolox_24p/exp/yolox_base.py:120-124: SGD momentum 0.9 nesterov, no decay)
+ * a11  optimizer (yolox_24p/exp/yolox_base.py:120-124: SGD momentum 0.9 nesterov, no decay - the default; the
+ *      *_decay entry points below add stock YOLOX's weight decay by parameter group, yolox/exp/yolox_base.py:198-224)
  * ------------------------------------------------------------------------------------------------ */
 /* flat fp32 p/g/buf of n elements: buf = first ? g : m*buf+g ; p -= lr*(g + m*buf); g is scaled by
  * grad_scale first (1/world for data parallel means).  `first` is read from *first_flag (device int32),
@@ -488,6 +489,23 @@ int ep24_ema_update(float* ema, const float* src, int64_t n, float decay, float 
 /* writes hp[0..4] on the stream (by-value arguments: no host buffer has to outlive the call). */
 int ep24_set_hparams(float* hp, float lr, float momentum, float grad_scale, float ema_decay, float one_minus_decay,
                      void* stream);
+/* Weight decay by parameter group (torch.optim.SGD(momentum, nesterov=True, weight_decay), dampening 0), in the same one pass.
+ * decay_grp has one byte per 64 elements of the WHOLE flat buffer, indexed (first + i) >> 6 exactly as wf_delta is: non-zero = the
+ * group decays (segments start at multiples of 64 elements, so a group lies in one segment).  Per element, every product and sum
+ * rounded to fp32 on its own, the gradient scaled first:
+ *     gs = g * grad_scale;   d = decays ? gs + weight_decay * p : gs;   b' = first ? d : m*b + d;   p' = p - lr*(d + m*b')
+ * (the decay product is not formed for a group that does not decay: those elements get the bits of the entry points above).  The
+ * EMA and the packed forward copy are made from p' as before.  A null decay_grp is EP24_E_ARG.
+ * ep24_set_hparams_decay writes hp[0..5], hp[5] = weight_decay; ep24_sgd_nesterov_decay is the by-value form (whole buffer, clears
+ * first_flag); ep24_sgd_nesterov_decay_hp_range_pack reads hp[0..5] and takes nullable ema and nullable wf_delta / wf (both or
+ * neither), so it stands for the _hp, _hp_range and _hp_range_pack forms. */
+int ep24_set_hparams_decay(float* hp, float lr, float momentum, float grad_scale, float ema_decay, float one_minus_decay,
+                           float weight_decay, void* stream);
+int ep24_sgd_nesterov_decay(float* p, const float* g, float* buf, int64_t n, float lr, float momentum, float grad_scale,
+                            float weight_decay, const uint8_t* decay_grp, int32_t* first_flag, void* stream);
+int ep24_sgd_nesterov_decay_hp_range_pack(float* p, const float* g, float* buf, int64_t first, int64_t n, const float* hp,
+                                          int32_t* first_flag, float* ema, int last, const int32_t* wf_delta, void* wf,
+                                          const uint8_t* decay_grp, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * a13  fisheye sector warp (yolox/demo_featuremap.py:244-328)
