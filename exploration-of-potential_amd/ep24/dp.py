@@ -88,6 +88,7 @@ class GradReducer:
         if self.world > 1:
             for buf in (home.flat, home.mflat, home.bflat, home.first_flag):
                 broadcast_parameters(buf, 0, self.group)
+            home.mark_weights_changed()                    # the masters were written behind the fused update's back
 
     def cuts(self, eng=None):
         return list(self._cuts)

@@ -18,6 +18,10 @@ backward) over pre-allocated NHWC bf16 buffers:
 The lists contain no host synchronisation, no allocation and no shape-dependent Python, so a training step
 is captured into a hipGraph (``ep24.train.TrainStep``).
 """
+import bisect
+import collections
+import struct
+
 import torch
 
 from . import _lib, nn as enn
@@ -63,9 +67,6 @@ class Dyn:
 
     def get(self):
         return self.table[self.key]
-
-
-_PENDING_GW = []
 
 
 class Act:
@@ -117,14 +118,8 @@ class Act:
         r = self._groot()
         return r.buf.gwritten, r.c0, r.c0 + r.C
 
-    def gregion(self):
-        """(gradient buffer identity, first channel, one past the last) of this Act's gradient."""
-        r = self._groot()
-        return (id(r.buf), r.c0, r.c0 + r.C)
-
     def gwrite(self):
         """Called while the backward list is built: 0 = first producer (overwrite), 1 = accumulate."""
-        _PENDING_GW.append(self.gregion())           # picked up by the next Engine._b(): that entry writes this region
         w, lo, hi = self._interval()
         if any(a <= lo and hi <= b for a, b in w):
             return 1
@@ -143,6 +138,21 @@ class Act:
     def gready(self):
         w, lo, hi = self._interval()
         return any(a <= lo and hi <= b for a, b in w)
+
+
+class Unit:
+    """What the pieces of one conv -> BatchNorm -> activation unit share: input ``x``, raw conv output ``z`` (the BatchNorm's input),
+    activated output ``out`` (``M`` pixels x ``C`` channels); ``seg`` / ``gam`` / ``bet`` (the parameters' segments); ``save`` (batch
+    statistics), ``stats`` / ``sum_g`` / ``sum_b`` (scratch slots); ``act``; a dense conv adds its geometry (Engine.unit) and, while
+    backward is built, ``idx`` and ``dz``."""
+    fused = 0                                    # channels whose BatchNorm-backward sums a consumer's input gradient produces
+
+    def __init__(self, **fields):
+        self.__dict__.update(fields)
+
+
+# arguments of ep24_bn_act_fwd in the kernel's order: a consumer that absorbs the pass (ep24_conv1x1_bnin_bf16) reads them by name
+BnPass = collections.namedtuple("BnPass", "z ldz stats reps gam bet rm rv nbt nbt2 save y ldy res ldres M C eps mom act")
 
 
 # ------------------------------------------------------------------------------------------------ parameters
@@ -174,20 +184,34 @@ class ParamHome:
         if dev.type != "cuda":
             raise _lib.Ep24Error("ep24: move the model to the GPU before running it (model.to('cuda'))")
         self.dev = dev
+        self._collect_segments(model)
+        self._lay_out()
+        self._build_update_tables()
+        self._build_pack_tables()
+        self._home_bn_statistics(model)
+        self._rehome_parameters(model)
+
+    def _collect_segments(self, model):
+        """One ConvSeg / VecSeg per launch that owns parameters, in execution order."""
         self.convs, self.vecs, self.order, self.by_param = [], [], [], {}
         self.merged_bn = []                               # (bn of conv2, bn of conv1) of the merged CSP units
         stems = {m.conv for m in model.modules() if isinstance(m, enn.Focus)}
+        def conv_seg(w, stem=False, depthwise=False):
+            k = w.shape[2]
+            if stem:              # an image stem runs as im2col rows x [Cout][k*k*Cin] (Focus: [Cout][108]): one "tap" of k*k*Cin columns
+                return ConvSeg([w], w.shape[0], 1, k * k * w.shape[1], need_dgrad=False)
+            if depthwise:         # DWConv.dconv: [C][9] fp32, the kernels read the master itself
+                return ConvSeg([w], w.shape[0], k * k, 1, need_dgrad=False)
+            return ConvSeg([w], w.shape[0], k * k, w.shape[1])
+
+        def add_unit(seg, *bns):                                     # a conv segment, then its BatchNorm's (merged pair: both) weights and biases
+            self._add(seg)
+            self._add(VecSeg([b.weight for b in bns]))
+            self._add(VecSeg([b.bias for b in bns]))
+
         for mod in exec_order(model, self.options):
             if isinstance(mod, tuple) and mod[0] == "unit":          # (conv, bn) pair of a swapped backbone
-                _, conv, bn_, stem = mod
-                w = conv.weight
-                k = w.shape[2]
-                if stem:                                             # im2col rows x [Cout][k*k*Cin]
-                    self._add(ConvSeg([w], w.shape[0], 1, k * k * w.shape[1], need_dgrad=False))
-                else:
-                    self._add(ConvSeg([w], w.shape[0], k * k, w.shape[1]))
-                self._add(VecSeg([bn_.weight]))
-                self._add(VecSeg([bn_.bias]))
+                add_unit(conv_seg(mod[1].weight, stem=mod[3]), mod[2])
             elif isinstance(mod, tuple) and mod[0] == "unused":      # in the state dict, not in the graph: gradient stays 0
                 self._add(VecSeg([mod[1]]))
                 self.order[-1].unused = True                         # never decays either: torch skips a parameter without a gradient
@@ -195,29 +219,15 @@ class ParamHome:
                 # two BaseConv units over the same input as one GEMM + one BN launch; (first, second) = channel order of the output
                 c2, c1 = (mod[1].conv2, mod[1].conv1) if mod[0] == "csp_merged" else (mod[1], mod[2])
                 w2, w1 = c2.conv.weight, c1.conv.weight
-                self._add(ConvSeg([w2, w1], w2.shape[0] + w1.shape[0], w2.shape[2] * w2.shape[3], w2.shape[1]))
-                self._add(VecSeg([c2.bn.weight, c1.bn.weight]))
-                self._add(VecSeg([c2.bn.bias, c1.bn.bias]))
+                add_unit(ConvSeg([w2, w1], w2.shape[0] + w1.shape[0], w2.shape[2] * w2.shape[3], w2.shape[1]), c2.bn, c1.bn)
                 self.merged_bn.append((c2.bn, c1.bn))
             elif isinstance(mod, tuple) and mod[0] == "conv":        # a conv on its own (DenseNet: BN sits in front of it)
-                w = mod[1].weight
-                k = w.shape[2]
-                self._add(ConvSeg([w], w.shape[0], 1, k * k * w.shape[1], need_dgrad=False) if mod[2] else
-                          ConvSeg([w], w.shape[0], k * k, w.shape[1]))
+                self._add(conv_seg(mod[1].weight, stem=mod[2]))
             elif isinstance(mod, tuple) and mod[0] == "bn":
                 self._add(VecSeg([mod[1].weight]))
                 self._add(VecSeg([mod[1].bias]))
             elif isinstance(mod, enn.BaseConv):
-                w = mod.conv.weight
-                k = w.shape[2]
-                if mod in stems:      # Focus stem runs as im2col x [Cout][108]: one "tap" of 108 (kh,kw,c) columns
-                    self._add(ConvSeg([w], w.shape[0], 1, k * k * w.shape[1], need_dgrad=False))
-                elif mod.conv.groups > 1:                  # depthwise (DWConv.dconv): [C][9] fp32, the kernels read the master itself
-                    self._add(ConvSeg([w], w.shape[0], k * k, 1, need_dgrad=False))
-                else:
-                    self._add(ConvSeg([w], w.shape[0], k * k, w.shape[1]))
-                self._add(VecSeg([mod.bn.weight]))
-                self._add(VecSeg([mod.bn.bias]))
+                add_unit(conv_seg(mod.conv.weight, stem=mod in stems, depthwise=mod.conv.groups > 1), mod.bn)
             elif isinstance(mod, enn.YOLOXHead):
                 for k in range(len(mod.stems)):
                     rw, ow, cw = mod.reg_preds[k].weight, mod.obj_preds[k].weight, mod.cls_preds[k].weight
@@ -229,6 +239,10 @@ class ParamHome:
         missing = [n for n, p in model.named_parameters() if p not in self.by_param]
         if missing:
             raise _lib.Ep24Error("ep24: parameters outside the supported graph: %s" % missing[:4])
+
+    def _lay_out(self):
+        """Offsets of every segment in the flat buffers and of every conv segment in the two packed copies; allocates them."""
+        dev = self.dev
         n = wf = wd = 0
         for seg in self.order:                      # execution order: backward completes the buffer from its tail
             seg.off = n
@@ -246,6 +260,10 @@ class ParamHome:
         self.wf = torch.zeros(max(wf, 8), dtype=BF16, device=dev)
         self.wd = torch.zeros(max(wd, 8), dtype=BF16, device=dev)
         self.first_flag = torch.ones(1, dtype=torch.int32, device=dev)
+
+    def _build_update_tables(self):
+        """The per-64-element tables the fused update reads: ``wf_delta`` and ``decay_grp``."""
+        n, dev = self.numel, self.dev
         # Round 5: the fused update writes the packed forward copy itself (csrc/elementwise.hip sgd_kernel).  One int32 per 64 flat
         # elements: (offset of the element's segment in wf) - (its offset in flat) for a conv weight whose Cin is a multiple of 8
         # (its [Cout][T][Cin] master IS the packed layout), INT32_MIN otherwise (BatchNorm vectors, biases, padded-Cin convs: the
@@ -267,22 +285,45 @@ class ParamHome:
         # biases, unused parameters) never decay.  A segment's alignment padding belongs to its group: zeros, which decay to zeros.
         self.decay_grp = torch.zeros(max(n // 64, 1), dtype=torch.uint8, device=dev)
         self.set_decay_params([p for seg in self.convs for p in seg.params])
+
+    @staticmethod
+    def _pack_rows(segs):
+        """Descriptor rows of the packing kernel for ``segs`` with the prefix sums of their elements and of their transpose tiles."""
+        rows, pref, tpref = [], [0], [0]
+        for seg in segs:
+            rows.append([seg.off, seg.wf_off, seg.wd_off if seg.need_dgrad else -1, seg.cout, seg.taps, seg.cin, seg.cin_pad, seg.cout_pad])
+            pref.append(pref[-1] + seg.numel)
+            tpref.append(tpref[-1] + seg.taps * ((seg.cout + 63) // 64) * ((seg.cin + 63) // 64))
+        return rows, pref, tpref
+
+    def _build_pack_tables(self):
+        """Descriptor tables of the packing kernel (built now: the calls sit inside captured graphs): all conv segments, and the
+        ``pack_rest`` segments on their own."""
+        dev = self.dev
+        t = lambda v: torch.tensor(v, dtype=torch.int64, device=dev)
         self._rest_tables = None
-        if self.pack_rest:                                # descriptor tables of the packing kernel for just those segments (built now:
-            rows, pref, tpref = [], [0], [0]              # the call sits inside captured graphs)
-            for seg in self.pack_rest:
-                rows.append([seg.off, seg.wf_off, seg.wd_off if seg.need_dgrad else -1, seg.cout, seg.taps, seg.cin, seg.cin_pad, seg.cout_pad])
-                pref.append(pref[-1] + seg.numel)
-                tpref.append(tpref[-1] + seg.taps * ((seg.cout + 63) // 64) * ((seg.cin + 63) // 64))
-            t = lambda v: torch.tensor(v, dtype=torch.int64, device=dev)
+        if self.pack_rest:
+            rows, pref, tpref = self._pack_rows(self.pack_rest)
             self._rest_tables = (t(rows), t(pref), t(tpref), len(rows), pref[-1], tpref[-1])
-        # BatchNorm running statistics in one flat buffer too (module buffers become views): ModelEMA averages every
-        # floating-point state_dict entry (utils/ema.py:55-60), i.e. these next to the parameters, in two launches
+        rows, pref, tpref = self._pack_rows(self.convs)
+        self.pack_desc, self.pack_prefix, self.pack_tprefix = t(rows), t(pref), t(tpref)
+        self.pack_total, self.pack_tiles = pref[-1], tpref[-1]
+        # lookup tables of the packing kernels: segment of every 4096-element chunk / of every transpose tile (built once)
+        self.pack_chunk_seg = torch.tensor([bisect.bisect_right(pref, c * 4096) - 1 for c in range((pref[-1] + 4095) // 4096)] or [0],
+                                           dtype=torch.int32, device=dev)
+        tseg = []
+        for si in range(len(self.convs)):
+            tseg += [si] * (tpref[si + 1] - tpref[si])
+        self.pack_tile_seg = torch.tensor(tseg or [0], dtype=torch.int32, device=dev)
+
+    def _home_bn_statistics(self, model):
+        """BatchNorm running statistics in one flat buffer too (module buffers become views): ModelEMA averages every
+        floating-point state_dict entry (utils/ema.py:55-60), i.e. these next to the parameters, in two launches."""
         paired = {id(b) for pair in self.merged_bn for b in pair}
         groups = [[m] for m in model.modules() if isinstance(m, torch.nn.BatchNorm2d) and id(m) not in paired]
         groups += [list(pair) for pair in self.merged_bn]     # [rm2 | rm1 | rv2 | rv1]: one BN launch covers both
         nb = sum((b.num_features + 3) // 4 * 8 for g in groups for b in g)
-        self.bflat = torch.zeros(max(nb, 4), dtype=torch.float32, device=dev)
+        self.bflat = torch.zeros(max(nb, 4), dtype=torch.float32, device=self.dev)
         self.bnumel = nb
         o = 0
         with torch.no_grad():
@@ -295,24 +336,9 @@ class ParamHome:
                         v.copy_(getattr(b, name))
                         setattr(b, name, v)
                         o += (c + 3) // 4 * 4
-        rows, pref, tpref = [], [0], [0]
-        for seg in self.convs:
-            rows.append([seg.off, seg.wf_off, seg.wd_off if seg.need_dgrad else -1, seg.cout, seg.taps, seg.cin, seg.cin_pad, seg.cout_pad])
-            pref.append(pref[-1] + seg.numel)
-            tpref.append(tpref[-1] + seg.taps * ((seg.cout + 63) // 64) * ((seg.cin + 63) // 64))
-        self.pack_tprefix = torch.tensor(tpref, dtype=torch.int64, device=dev)
-        self.pack_tiles = tpref[-1]
-        # lookup tables of the packing kernels: segment of every 4096-element chunk / of every transpose tile (built once)
-        import bisect
-        self.pack_chunk_seg = torch.tensor([bisect.bisect_right(pref, c * 4096) - 1 for c in range((pref[-1] + 4095) // 4096)] or [0],
-                                           dtype=torch.int32, device=dev)
-        tseg = []
-        for si in range(len(self.convs)):
-            tseg += [si] * (tpref[si + 1] - tpref[si])
-        self.pack_tile_seg = torch.tensor(tseg or [0], dtype=torch.int32, device=dev)
-        self.pack_desc = torch.tensor(rows, dtype=torch.int64, device=dev)
-        self.pack_prefix = torch.tensor(pref, dtype=torch.int64, device=dev)
-        self.pack_total = pref[-1]
+
+    def _rehome_parameters(self, model):
+        """Every parameter (and its .grad) becomes a view of the flat buffers; whatever was planned for parts of the tree is stale."""
         for sub in model.modules():                       # load_state_dict writes parameters behind the fused update's back
             if not getattr(sub, "_ep24_pack_hook", False):
                 sub.register_load_state_dict_post_hook(_weights_loaded)
@@ -395,6 +421,7 @@ class ParamHome:
         self.decay_grp.copy_(table)
 
     def sgd(self, lr, momentum, grad_scale=1.0, weight_decay=0.0):
+        self.mark_weights_changed()                       # this update does not write the packed forward copy
         if weight_decay:
             call("sgd_nesterov_decay", ptr(self.flat), ptr(self.gflat), ptr(self.mflat), self.numel, float(lr), float(momentum),
                  float(grad_scale), float(weight_decay), ptr(self.decay_grp), ptr(self.first_flag), stream_ptr())
@@ -472,9 +499,9 @@ def head_is_merged(head, opts):
 
 
 def exec_order(model, opts=None):
-    opts = opts if opts is not None else get_options(model)
     """Modules in the order the plan executes them (yolox.py:24-34 -> yolo_pafpn.py:83-124 -> yolo_head_24p.py:150-189);
     any other container (tests build single blocks) falls back to registration order."""
+    opts = opts if opts is not None else get_options(model)
     def head_order(head):
         for k in range(len(head.stems)):
             yield head.stems[k]
@@ -644,7 +671,6 @@ class Engine:
         self.unit_acts = {}                      # BaseConv module -> (input, raw conv output, activated output)
         self.fwd_eval = []                       # eval-mode forward (running-statistics BN, sigmoid head): SURVEY 8f N3
         self.bwd_writes = []                     # per backward launch: flat-gradient ranges it writes (for ep24.dp)
-        self.bwd_gw, self.bwd_rd = [], []        # per backward launch: activation-gradient regions written / the one a BN reduce reads
         self._bwd_units = 0
         self._cur_tag = None
         self._force_side = False
@@ -661,7 +687,7 @@ class Engine:
         self._dz_elems = 0
         self._slab_floats, self._pending_reduce, self._keep = 0, [], []
         self.head_grads = []                     # per head level: (cells per image, stride, d_regobj, d_cls)
-        self.skip_decode_bwd = False             # True: the loss wrote those rows itself, the head_decode_bwd entries are skipped
+        self._decode_levels = None
         self._wg_pending = {}                    # tile class -> weight-gradient problems waiting for their grouped launch
         self._wg_tail = False
         self._side = None
@@ -677,6 +703,9 @@ class Engine:
         self.origin = None                       # [B,A,26] raw regression outputs, filled while use_l1 is on
         self._stats_specs, self._sum_specs = [], []
         self.max_dz = 0
+        self.n_bnin = self.n_bnbwd = self.n_bnr_stream = 0      # how often each fused BatchNorm launch replaced its separate ones
+        self.drop_keep, self.drop_p, self.fixed_dropout = None, 0.0, False    # Dropout2d keep factors of a DenseNet plan
+        self.fwd_fork = self.fwd_fork1 = self.fwd_head0 = self.fwd_head1 = None   # where the forward lanes of ep24.train fork
         self._build()
 
     # ---- small helpers ----------------------------------------------------------------------------
@@ -704,15 +733,27 @@ class Engine:
         if ev is not False:                          # ev=False: a training-only launch (batch statistics, dropout)
             self.fwd_eval.append(ev if ev is not None else (name, args))
 
-    def _b(self, name, args, writes=(), reads=None):
+    def _side_later(self, emit):
+        """Inside the head levels that run on the side lane the weight gradients wait until the chain is through, so that the main
+        lane's join is not held up by work nothing depends on (every layer owns its dz)."""
+        if self._force_side:
+            self._deferred.append(emit)
+        else:
+            emit()
+
+    def _emit_deferred(self):
+        """The weight gradients of the side-lane chains: after the chains."""
+        self._force_side = False
+        for emit in self._deferred:
+            emit()
+        self._deferred = []
+
+    def _b(self, name, args, writes=()):
         name, args = self._kopt(name, args)
         if self._force_side and name[0] != "@" and not name.startswith("side:"):
             name = "side:" + name
         self.bwd.append((name, args))
         self.bwd_writes.append([(seg.off, seg.numel) for seg in writes])
-        self.bwd_gw.append(list(_PENDING_GW))        # activation-gradient regions this entry writes
-        del _PENDING_GW[:]
-        self.bwd_rd.append(reads.gregion() if reads is not None else None)
 
     # ---- graph construction -------------------------------------------------------------------------
     def _build(self):
@@ -801,7 +842,6 @@ class Engine:
         self.outputs = torch.zeros(B, self.A, self.ncols, dtype=torch.float32, device=self.dev)
         a0 = 0
         self.levels = []
-        self.fwd_head0 = None
         for k, feat in enumerate(feats):
             lo = len(self.fwd)
             self.head_level(head, k, feat, a0)
@@ -845,10 +885,7 @@ class Engine:
                     self._b("@side_wait_main", ())
                 if self._force_side and not want:
                     self.bwd_par_end = len(self.bwd)
-                    self._force_side = False
-                    for f in self._deferred:              # the weight gradients of the side-lane chains: after the chains
-                        f()
-                    self._deferred = []
+                    self._emit_deferred()
                 self._force_side = want
             in_head = is_head
             if b is self._bwd_builders[0] and len(self._bwd_builders) > 1:
@@ -857,12 +894,8 @@ class Engine:
                 self._flush_reduce()
                 self.bwd_tail_cut = len(self.bwd)
             b()
-        self._force_side = False
-        for f in self._deferred:
-            f()
-        self._deferred = []
+        self._emit_deferred()
         self._flush_reduce()
-        del _PENDING_GW[:]
         self.slab = torch.zeros(max(self._slab_floats, 4), dtype=torch.float32, device=self.dev)
         self.fold_w = torch.zeros(max(self._fold_w, 8), dtype=BF16, device=self.dev)
         self.fold_b = torch.zeros(max(self._fold_c, 4), dtype=torch.float32, device=self.dev)
@@ -923,22 +956,55 @@ class Engine:
             splits, _wg, _slots = self._wg_plan(probs, cls)
             rows = []
             for pr, sp in zip(probs, splits):
-                seg = pr["seg"]
-                soff = self._slab_floats
-                self._slab_floats += sp * seg.numel
-                rows.append((pr, sp, soff))
-                self._pending_reduce.append((seg, sp, soff))
+                soff, slab_p = self._slab_alloc(sp * pr["seg"].numel)
+                rows.append((pr, sp, slab_p))
+                self._pend_reduce(pr["seg"], sp, soff, flush=False)
             keep = self._keep
 
             def table(rows=rows):                      # resolved with the other launch arguments in _finalize: a HOST int64 array
-                t = torch.tensor([[pr["x"](), pr["ld_x"], pr["dz"](), pr["ld_dy"], self.slab.data_ptr() + 4 * soff, sp * pr["seg"].numel,
+                t = torch.tensor([[pr["x"](), pr["ld_x"], pr["dz"](), pr["ld_dy"], slab_p(), sp * pr["seg"].numel,
                                    pr["ld_dw"], pr["cout_valid"], pr["cin_valid"], pr["B"], pr["H"], pr["W"], pr["cin"], pr["cout"], pr["k"], pr["s"], sp]
-                                  for pr, sp, soff in rows], dtype=torch.int64)
+                                  for pr, sp, slab_p in rows], dtype=torch.int64)
                 keep.append(t)
                 return t.data_ptr()
             self._b("@side_wait_main", ())
             self._b("side:conv_wgrad_group_bf16", (table, len(rows)))
             self._b("@side_record", (probs[-1]["idx"],))
+
+    def _slab_alloc(self, floats):
+        """``floats`` floats of the weight-gradient slab -> (offset, pointer thunk: the slab itself is allocated in _finalize)."""
+        soff = self._slab_floats
+        self._slab_floats += floats
+        return soff, (lambda: self.slab.data_ptr() + 4 * soff)
+
+    def _pend_reduce(self, seg, splits, soff, flush=True):
+        """The ``splits`` partial gradients of ``seg`` at slab offset ``soff`` are folded by the next reduce launch, which goes out
+        once WGRAD_REDUCE_GROUP segments wait (``flush=False``: the caller's launches are not complete yet)."""
+        self._pending_reduce.append((seg, splits, soff))
+        if flush and len(self._pending_reduce) >= WGRAD_REDUCE_GROUP:
+            self._flush_reduce()
+
+    def _layer_wgrad(self, name, seg, splits, idx, args):
+        """One layer's weight gradient as a launch of its own on the side lane, behind what the main lane has produced so far: the
+        partial sums of its pixel splits go to a slab slice with plain stores (no atomics: bitwise reproducible), a reduce launch
+        every few layers folds them into the flat gradient in a fixed order.  ``args(slab pointer, floats)`` -> the launch arguments."""
+        assert splits >= 1, splits
+        soff, slab_p = self._slab_alloc(splits * seg.numel)
+        self._b("@side_wait_main", ())
+        self._b("side:" + name, args(slab_p, splits * seg.numel))
+        self._b("@side_record", (idx,))
+        self._pend_reduce(seg, splits, soff)
+
+    def _conv_wgrad_args(self, seg, x, dy, ld_dy, cin, cout, k, s):
+        """Arguments of ep24_conv_wgrad_slab_bf16 for ``seg`` over input ``x`` and output gradient ``dy`` (``cout``: its padded width)."""
+        return lambda slab_p, floats: (x.ptr(), x.ld, dy, ld_dy, slab_p, floats, seg.taps * seg.cin, seg.cout, seg.cin,
+                                       x.B, x.H, x.W, cin, cout, k, s)
+
+    def _bwd_slot(self, elems=0):
+        """-> (a unit's position in backward order: the key of its @side_record event, pointer thunk of its own dz slice)."""
+        idx, off = self._bwd_units, self._dz_elems
+        self._bwd_units, self._dz_elems = idx + 1, off + elems
+        return idx, (lambda: self.dzbuf.data_ptr() + (4 if self.f32 else 2) * off)
 
     def _flush_reduce(self):
         """One reduce launch (side stream, behind the weight-gradient kernels it sums) for the pending layers."""
@@ -977,67 +1043,72 @@ class Engine:
             return self.unit(mod.pconv, self.unit_dw(mod.dconv, x), out=out, residual=residual)
         return self.unit(mod, x, out=out, residual=residual, x_single=x_single)
 
+    # ---- BatchNorm passes shared by every kind of unit ------------------------------------------------
+    def _bn_fwd(self, bn, u, src, ld_src, stats, res_p=None, res_ld=0, bn2=None, infer=True):
+        """BatchNorm (batch statistics) + activation (+ residual) of ``src`` into ``u.out`` as one streaming launch; eval mode: the
+        same from the running statistics (``infer=False``: the conv in front of it has the BatchNorm folded in).  -> the BnPass."""
+        flat = self.home.flat
+        p = BnPass(src, ld_src, stats, STATS_REPLICAS, ptr(flat, u.gam.off), ptr(flat, u.bet.off), ptr(bn.running_mean), ptr(bn.running_var),
+                   ptr(bn.num_batches_tracked), ptr(bn2.num_batches_tracked) if bn2 is not None else None, ptr(u.save),
+                   u.out.ptr(), u.out.ld, res_p, res_ld, u.M, u.C, float(bn.eps), float(bn.momentum), u.act)
+        self._f("bn_act_fwd", *p, ev=("bn_act_infer", (p.z, p.ldz, p.gam, p.bet, p.rm, p.rv, p.y, p.ldy, p.res, p.ldres, p.M, p.C, p.eps, p.act))
+                if infer else False)
+        return p
+
+    def _bn_bwd_args(self, u):
+        """The leading arguments of every BatchNorm-backward kernel: dy, the BatchNorm's input, its saved statistics, parameters, sums."""
+        flat = self.home.flat
+        return (u.out.gptr(), u.out.gld, u.z.ptr(), u.z.ld, ptr(u.save), ptr(flat, u.gam.off), ptr(flat, u.bet.off), u.sum_g, u.sum_b)
+
+    def _bn_bwd_reduce(self, u):
+        self._b("bn_act_bwd_reduce", self._bn_bwd_args(u) + (u.M, u.C, u.act, STATS_REPLICAS))
+
+    def _bn_bwd_apply(self, u, dz, ld_dz, name="bn_act_bwd_apply", tail=()):
+        """The second pass (gamma / beta gradients and dz); ``name`` / ``tail``: the forms that do both passes in one launch."""
+        gflat = self.home.gflat
+        self._b(name, self._bn_bwd_args(u) + (ptr(gflat, u.gam.off), ptr(gflat, u.bet.off), dz, ld_dz, u.M, u.C, u.act, STATS_REPLICAS) + tail,
+                writes=(u.gam, u.bet))
+
+    def _new_unit(self, x, seg, bn, act, C, OH, OW, out=None):
+        """The record the pieces of one unit share: segments, buffers and scratch slots of conv -> BatchNorm -> activation."""
+        home = self.home
+        u = Unit(x=x, seg=seg, gam=home.by_param[bn.weight], bet=home.by_param[bn.bias], act=act, C=C, M=x.B * OH * OW,
+                 out=self.new_act(C, OH, OW) if out is None else out, z=self.new_act(C, OH, OW))
+        assert (u.out.H, u.out.W, u.out.C) == (OH, OW, C)
+        u.z.needs_grad = False
+        self.max_dz = max(self.max_dz, u.M * C)
+        u.save = torch.zeros(2 * C, dtype=torch.float32, device=self.dev)
+        u.stats = self._stats_slot(C)
+        u.sum_g, u.sum_b = self._sums_slot(C)
+        return u
+
     def unit_dw(self, mod, x):
         """A depthwise BaseConv (groups = channels): conv -> BN(batch stats) -> SiLU with the conv as HBM-bound elementwise kernels
         (csrc/dwconv.hip) over the fp32 master weights; BatchNorm + activation are the launches of every other unit."""
         if self.f32:
             raise NotImplementedError("ep24: the fp32 parity mode covers the dense network (the BASELINE configurations); depthwise variants run in bf16")
-        home = self.home
-        conv, bn, act = mod.conv, mod.bn, mod.act_code
-        seg = home.by_param[conv.weight]
-        gam, bet = home.by_param[bn.weight], home.by_param[bn.bias]
+        conv, bn = mod.conv, mod.bn
+        seg = self.home.by_param[conv.weight]
         k, s, C = conv.kernel_size[0], conv.stride[0], x.C
         assert (seg.cout, seg.cin, seg.taps) == (C, 1, 9), (seg.cout, seg.cin, seg.taps, C)
         B, H, W = x.B, x.H, x.W
-        OH, OW = (H - 1) // s + 1, (W - 1) // s + 1
-        out, z = self.new_act(C, OH, OW), self.new_act(C, OH, OW)
-        z.needs_grad = False
-        M = B * OH * OW
-        self.max_dz = max(self.max_dz, M * C)
-        save = torch.zeros(2 * C, dtype=torch.float32, device=self.dev)
-        stats = self._stats_slot(C)
-        sum_g, sum_b = self._sums_slot(C)
-        flat, gflat = home.flat, home.gflat
-        w_p = ptr(flat, seg.off)
+        u = self._new_unit(x, seg, bn, mod.act_code, C, (H - 1) // s + 1, (W - 1) // s + 1)
+        z, out = u.z, u.out
+        w_p = ptr(self.home.flat, seg.off)
         # eval mode: the same conv without statistics, then BatchNorm from the running statistics (not folded: the weights are the masters)
-        self._f("dwconv_fwd_bf16", x.ptr(), x.ld, w_p, z.ptr(), z.ld, stats, STATS_REPLICAS, B, H, W, C, k, s,
+        self._f("dwconv_fwd_bf16", x.ptr(), x.ld, w_p, z.ptr(), z.ld, u.stats, STATS_REPLICAS, B, H, W, C, k, s,
                 ev=("dwconv_fwd_bf16", (x.ptr(), x.ld, w_p, z.ptr(), z.ld, None, 1, B, H, W, C, k, s)))
-        self._f("bn_act_fwd", z.ptr(), z.ld, stats, STATS_REPLICAS, ptr(flat, gam.off), ptr(flat, bet.off), ptr(bn.running_mean),
-                ptr(bn.running_var), ptr(bn.num_batches_tracked), None, ptr(save), out.ptr(), out.ld, None, 0, M, C, float(bn.eps),
-                float(bn.momentum), act,
-                ev=("bn_act_infer", (z.ptr(), z.ld, ptr(flat, gam.off), ptr(flat, bet.off), ptr(bn.running_mean), ptr(bn.running_var),
-                                     out.ptr(), out.ld, None, 0, M, C, float(bn.eps), act)))
+        self._bn_fwd(bn, u, z.ptr(), z.ld, u.stats)
         self.unit_acts[mod] = (x, z, out)
 
         def build_bwd():
             assert out.gready(), "activation without a gradient producer"
-            kk = self._bwd_units
-            self._bwd_units += 1
-            dzoff = self._dz_elems
-            self._dz_elems += M * C
-            dz = (lambda dzoff=dzoff: self.dzbuf.data_ptr() + 2 * dzoff)
-            self._b("bn_act_bwd_reduce", (out.gptr(), out.gld, z.ptr(), z.ld, ptr(save), ptr(flat, gam.off), ptr(flat, bet.off), sum_g, sum_b,
-                                          M, C, act, STATS_REPLICAS), reads=out)
-            self._b("bn_act_bwd_apply", (out.gptr(), out.gld, z.ptr(), z.ld, ptr(save), ptr(flat, gam.off), ptr(flat, bet.off), sum_g, sum_b,
-                                         ptr(gflat, gam.off), ptr(gflat, bet.off), dz, C, M, C, act, STATS_REPLICAS), writes=(gam, bet))
+            idx, dz = self._bwd_slot(u.M * C)
+            self._bn_bwd_reduce(u)
+            self._bn_bwd_apply(u, dz, C)
             splits = _lib.lib().fn["ep24_dwconv_wgrad_splits"](B, H, W, C, s)
-            assert splits >= 1, splits
-
-            def emit_wgrad():                         # side lane: per-workgroup partial sums, folded by the next reduce launch
-                soff = self._slab_floats
-                self._slab_floats += splits * seg.numel
-                self._b("@side_wait_main", ())
-                self._b("side:dwconv_wgrad_slab_bf16", (x.ptr(), x.ld, dz, C, (lambda soff=soff: self.slab.data_ptr() + 4 * soff),
-                                                         splits * seg.numel, B, H, W, C, k, s))
-                self._b("@side_record", (kk,))
-                self._pending_reduce.append((seg, splits, soff))
-                if len(self._pending_reduce) >= WGRAD_REDUCE_GROUP:
-                    self._flush_reduce()
-
-            if self._force_side:
-                self._deferred.append(emit_wgrad)
-            else:
-                emit_wgrad()
+            self._side_later(lambda: self._layer_wgrad("dwconv_wgrad_slab_bf16", seg, splits, idx, lambda slab_p, floats: (
+                x.ptr(), x.ld, dz, C, slab_p, floats, B, H, W, C, k, s)))
             if x.needs_grad:
                 acc = x.gwrite()
                 self._b("dwconv_dgrad_bf16", (dz, C, w_p, x.gptr(), x.gld, acc, B, H, W, C, k, s))
@@ -1051,216 +1122,180 @@ class Engine:
         caller states that this unit is the only consumer of ``x`` (a Bottleneck's 3x3 over its 1x1): its input gradient IS the
         dy of the unit that produced x, and a 3x3 stride-1 one then takes that unit's BatchNorm-backward sums in its epilogue
         (ep24_conv_dgrad_bnr_bf16) instead of a reduce launch re-reading dy and z."""
-        home = self.home
         if act is None:                            # a BaseConv carries its activation (silu / relu / lrelu); merged pairs: the first module's
             act = getattr(mod, "act_code", 1)
         conv = mod.conv if conv is None else conv
         bn = mod.bn if bn is None else bn
-        seg = home.by_param[conv.weight]
-        gam, bet = home.by_param[bn.weight], home.by_param[bn.bias]
+        seg = self.home.by_param[conv.weight]
         focus = stem == "focus"                   # the Focus stem over the space-to-depth image (16 channels, 12 real): its own kernels
-        k = k_ = 1 if stem else conv.kernel_size[0]
-        s = 1 if stem else conv.stride[0]
-        cin = x.C                                  # stem: im2col width 112 (108 real columns)
+        k, s = (1, 1) if stem else (conv.kernel_size[0], conv.stride[0])       # stem: im2col rows x GEMM (width 112, 108 real columns)
         assert (x.C == 16 and (x.ld, seg.cin) == (16, 108)) if focus else x.C == seg.cin_pad if stem else x.C == seg.cin, (x.C, seg.cin)
-        cout = seg.cout
-        B, H, W = x.B, x.H, x.W
-        OH, OW = (H - 1) // s + 1, (W - 1) // s + 1
-        if out is None:
-            out = self.new_act(cout, OH, OW)
-        assert (out.H, out.W, out.C) == (OH, OW, cout)
-        z = self.new_act(cout, OH, OW)
-        z.needs_grad = False
-        M = B * OH * OW
-        self.max_dz = max(self.max_dz, M * cout)
-        save = torch.zeros(2 * cout, dtype=torch.float32, device=self.dev)
-        stats = self._stats_slot(cout)
-        sum_g, sum_b = self._sums_slot(cout)
-        flat, gflat = home.flat, home.gflat
-        wf = ptr(home.wf, seg.wf_off)              # stem: master row [108] zero padded to the im2col width
-        res_p = residual.ptr() if residual is not None else None
-        res_ld = residual.ld if residual is not None else 0
-        if self.f32:
-            if bn2 is not None:
-                self._f("incr_i64", ptr(bn2.num_batches_tracked), ev=False)
-            return self._unit_f32(mod, conv, bn, seg, gam, bet, x, z, out, residual, res_p, res_ld, k_, s, act, save, sum_g)
-        if self.fold_bn_eval:
-            woff, coff = self._fold_w, self._fold_c
-            self._fold_w += cout * seg.taps * seg.cin_pad
-            self._fold_c += cout
-            self._fold_units.append((seg, gam, bet, bn, woff, coff))
-            fw, fb = (lambda woff=woff: self.fold_w.data_ptr() + 2 * woff), (lambda coff=coff: self.fold_b.data_ptr() + 4 * coff)
-            if focus:
-                assert residual is None
-                ev_conv = ("stem_conv_fwd_infer_bf16", (x.ptr(), fw, seg.cin_pad, fb, act, out.ptr(), out.ld, B, H, W, cout))
-            else:
-                ev_conv = ("conv_fwd_infer_bf16", (x.ptr(), x.ld, fw, fb, act, res_p, res_ld, out.ptr(), out.ld, B, H, W, cin, cout, k, s))
-        elif focus:
-            ev_conv = ("stem_conv_fwd_bf16", (x.ptr(), wf, seg.cin_pad, z.ptr(), z.ld, None, 1, B, H, W, cout))
-        else:
-            ev_conv = ("conv_fwd_bf16", (x.ptr(), x.ld, wf, z.ptr(), z.ld, 0, 0, 0, None, None, 1, B, H, W, cin, cout, k, s))
-        xf_ok = (not stem and k == 1 and s == 1 and act == 1 and cout % 8 == 0 and
-                 _lib.lib().fn["ep24_conv1x1_xf_ok"](B, H, W, cin, cout) == 1)       # a shape of the transformed-A streaming kernel
-        prev = getattr(x, "_bnf", None) if bn_in and self.options.fuse_bn_stream and xf_ok else None
-        if prev is not None and prev[0] == len(self.fwd) - 1 and self.fwd[-1][0] == "bn_act_fwd" and prev[1][-1] == 1:
-            # The BatchNorm pass that produced x is the launch just before this one and this unit streams x through registers: it makes
-            # x itself (same expressions, same stored bytes) - the pass leaves the training list; the eval list keeps its own entries.
-            (pz, pldz, pstats, preps, pgam, pbet, prm, prv, pnbt, pnbt2, psave, py, pldy, pres, pldres, pM, pC, peps, pmom, _pact) = prev[1]
-            assert (py, pldy, pM, pC) == (x.ptr(), x.ld, M, cin)
-            self.fwd.pop()
-            self.fwd.append(("conv1x1_bnin_bf16", (pz, pldz, pstats, preps, pgam, pbet, prm, prv, pnbt, pnbt2, psave, py, pldy, pres, pldres,
-                                                   peps, pmom, 1, wf, z.ptr(), z.ld, stats, STATS_REPLICAS, B, H, W, cin, cout)))
-            self.fwd_eval.append(ev_conv)
-            self.n_bnin = getattr(self, "n_bnin", 0) + 1
-        elif focus:
-            self._f("stem_conv_fwd_bf16", x.ptr(), wf, seg.cin_pad, z.ptr(), z.ld, stats, STATS_REPLICAS, B, H, W, cout, ev=ev_conv)
-        else:
-            self._f("conv_fwd_bf16", x.ptr(), x.ld, wf, z.ptr(), z.ld, 0, 0, 0, None, stats, STATS_REPLICAS, B, H, W, cin, cout, k, s, ev=ev_conv)
-        bn_args = (z.ptr(), z.ld, stats, STATS_REPLICAS, ptr(flat, gam.off), ptr(flat, bet.off),
-                   ptr(bn.running_mean), ptr(bn.running_var), ptr(bn.num_batches_tracked),
-                   ptr(bn2.num_batches_tracked) if bn2 is not None else None, ptr(save), out.ptr(), out.ld,
-                   res_p, res_ld, M, cout, float(bn.eps), float(bn.momentum), act)
-        self._f("bn_act_fwd", *bn_args,
-                ev=False if self.fold_bn_eval else
-                ("bn_act_infer", (z.ptr(), z.ld, ptr(flat, gam.off), ptr(flat, bet.off), ptr(bn.running_mean),
-                                  ptr(bn.running_var), out.ptr(), out.ld, res_p, res_ld, M, cout, float(bn.eps), act)))
-        out._bnf = (len(self.fwd) - 1, bn_args)        # where this output's BatchNorm pass sits (a consumer with bn_in may absorb it)
+        u = self._new_unit(x, seg, bn, act, seg.cout, (x.H - 1) // s + 1, (x.W - 1) // s + 1, out)
+        u.focus, u.stem, u.k, u.s, u.cin, u.bn = focus, stem, k, s, x.C, bn
+        u.res_p, u.res_ld = (residual.ptr(), residual.ld) if residual is not None else (None, 0)
+        out = u.out
         if residual is not None:
             residual.alias_grad(out)
-        self.unit_acts[mod if mod is not None else conv] = (x, z, out)
-        info = dict(z=z, save=save, gam=gam, bet=bet, sum_g=sum_g, sum_b=sum_b, act=act, cout=cout, fused=0)
+        self.unit_acts[mod if mod is not None else conv] = (x, u.z, out)
+        if self.f32:
+            return self._unit_f32(u, bn2)
+        self._unit_fwd(u, bn2, bn_in)
         # one launch for both BatchNorm-backward passes (PlanOptions.fuse_bn_bwd): trunk units only - while the head levels' backward
         # runs on the second lane its ring kernels hold whole CUs' LDS, and a workgroup that cannot be placed keeps the others waiting
-        one_launch = bool(self.options.fuse_bn_bwd) and not (self._cur_tag is not None and self._cur_tag[0] == "head") and cout <= 2048
-        bar = self._bar_slot() if one_launch else None
+        one_launch = bool(self.options.fuse_bn_bwd) and not (self._cur_tag is not None and self._cur_tag[0] == "head") and u.C <= 2048
+        u.bar = self._bar_slot() if one_launch else None
         if residual is None:                       # with a residual the incoming gradient is shared with the shortcut: not this unit's alone
-            out.bn_info, out.bn_c0 = info, 0
-        out.bn_any = info                          # ... which a consumer that states `below_in` knows how to complete
+            out.bn_info, out.bn_c0 = u, 0
+        out.bn_any = u                             # ... which a consumer that states `below_in` knows how to complete
 
         def build_bwd():
             assert out.gready(), "activation without a gradient producer"
-            k = self._bwd_units                       # position in backward execution order
-            self._bwd_units += 1
-            dgrad_done = False
-            dzoff = self._dz_elems
-            self._dz_elems += M * cout
-            dz = (lambda dzoff=dzoff: self.dzbuf.data_ptr() + 2 * dzoff)
-            assert info["fused"] in (0, cout), "BatchNorm-backward sums fused for a part of the channels only"
-            if one_launch and not info["fused"]:
-                self._b("bn_act_bwd_fused", (out.gptr(), out.gld, z.ptr(), z.ld, ptr(save), ptr(flat, gam.off), ptr(flat, bet.off), sum_g, sum_b,
-                                             ptr(gflat, gam.off), ptr(gflat, bet.off), dz, cout, M, cout, act, STATS_REPLICAS, bar),
-                        writes=(gam, bet), reads=out)
-            else:
-                if not info["fused"]:                 # else: the consumer's input-gradient epilogue has produced the two sums
-                    self._b("bn_act_bwd_reduce", (out.gptr(), out.gld, z.ptr(), z.ld, ptr(save), ptr(flat, gam.off),
-                                                  ptr(flat, bet.off), sum_g, sum_b, M, cout, act, STATS_REPLICAS), reads=out)
-                # The apply pass and the input gradient of a 1x1 unit of the streaming kernel as ONE launch (PlanOptions.fuse_bn_dgrad,
-                # ep24_conv1x1_dgrad_bnbwd_bf16): dz is made on the way to the MFMAs and stored for the weight gradient.
-                if xf_ok and self.options.fuse_bn_dgrad and x.needs_grad and not info["fused"] and seg.cout_pad == cout:
-                    acc = x.gwrite()
-                    self._b("conv1x1_dgrad_bnbwd_bf16", (out.gptr(), out.gld, z.ptr(), z.ld, ptr(save), ptr(flat, gam.off), ptr(flat, bet.off),
-                                                          sum_g, sum_b, ptr(gflat, gam.off), ptr(gflat, bet.off), dz, cout, act, STATS_REPLICAS,
-                                                          ptr(home.wd, seg.wd_off), x.gptr(), x.gld, acc, B, H, W, cin, cout), writes=(gam, bet))
-                    self.n_bnbwd = getattr(self, "n_bnbwd", 0) + 1
-                    dgrad_done = True
-                else:
-                    self._b("bn_act_bwd_apply", (out.gptr(), out.gld, z.ptr(), z.ld, ptr(save), ptr(flat, gam.off),
-                                                 ptr(flat, bet.off), sum_g, sum_b, ptr(gflat, gam.off), ptr(gflat, bet.off),
-                                                 dz, cout, M, cout, act, STATS_REPLICAS), writes=(gam, bet), reads=out if info["fused"] else None)
+            u.idx, u.dz = self._bwd_slot(u.M * u.C)
+            dgrad_done = self._unit_bn_bwd(u)
             # weight gradient on the side stream: it only needs dz and the saved input, and nothing on the main
             # stream needs its result before the optimizer, so it overlaps the dgrad and the next layer's BN passes
-            # partial sums of the pixel splits go to this layer's slab slice with plain stores; a reduce launch every
-            # few layers folds them into the flat gradient in a fixed order (no atomics: bitwise reproducible)
-            splits = _lib.lib().fn["ep24_stem_conv_wgrad_splits"](B, H, W, cout) if focus else \
-                self._wsplits(B, H, W, cin, cout, k_, s)
-            assert splits >= 1, splits
-
-            def emit_wgrad():
-                if self.options.group_wgrad and not focus and not self._wg_tail and not (self.options.conv_kernel_opts & 0x100):
-                    # grouped with the other layers of its tile class (csrc/conv_wgrad.hip wgrad_group_kernel); its slab is
-                    # allotted when the group is launched (the split count is the group's)
-                    self._pend_wgrad(dict(x=x.ptr, ld_x=x.ld, dz=dz, ld_dy=cout, ld_dw=seg.taps * seg.cin, cout_valid=cout, cin_valid=seg.cin,
-                                          B=B, H=H, W=W, cin=cin, cout=cout, k=k_, s=s, seg=seg, idx=k))
-                    if len(self._pending_reduce) >= WGRAD_REDUCE_GROUP:
-                        self._flush_reduce()
-                    return
-                soff = self._slab_floats
-                self._slab_floats += splits * seg.numel
-                self._b("@side_wait_main", ())
-                slab_p = (lambda soff=soff: self.slab.data_ptr() + 4 * soff)
-                if focus:
-                    self._b("side:stem_conv_wgrad_slab_bf16", (x.ptr(), dz, cout, slab_p, splits * seg.numel, B, H, W, cout))
-                else:
-                    self._b("side:conv_wgrad_slab_bf16", (x.ptr(), x.ld, dz, cout, slab_p,
-                                                          splits * seg.numel, seg.taps * seg.cin, cout, seg.cin, B, H, W, cin, cout, k_, s))
-                self._b("@side_record", (k,))
-                self._pending_reduce.append((seg, splits, soff))
-                if len(self._pending_reduce) >= WGRAD_REDUCE_GROUP:
-                    self._flush_reduce()
-
-            # inside the head levels that run on the side lane the weight gradients wait until the chain is through, so
-            # that the main lane's join is not held up by work nothing depends on (every layer owns its dz)
-            if self._force_side:
-                self._deferred.append(emit_wgrad)
-            else:
-                emit_wgrad()
+            self._side_later(lambda: self._unit_wgrad(u))
             if x.needs_grad and not dgrad_done:
-                acc = x.gwrite()
-                below = getattr(x, "bn_info", None) if x_single else None
-                if (below is not None and not acc and k_ == 3 and s == 1 and self.options.fuse_bn_reduce and x._alias is None and
-                        x.C % 8 == 0 and x.gld % 8 == 0 and below["z"].ld % 8 == 0):
-                    o, ct = x.bn_c0, below["cout"]
-                    zb, sv, gb, bb = below["z"], below["save"], below["gam"], below["bet"]
-                    self._b("conv_dgrad_bnr_bf16", (dz, cout, ptr(home.wd, seg.wd_off), x.gptr(), x.gld, B, H, W, cin, seg.cout_pad, k_,
-                                                    zb.ptr() + 2 * o, zb.ld, ptr(sv, o), ptr(sv, ct + o), ptr(flat, gb.off + o), ptr(flat, bb.off + o),
-                                                    (lambda f=below["sum_g"], o=o: f() + 8 * o), (lambda f=below["sum_b"], o=o: f() + 8 * o),
-                                                    2 * ct, STATS_REPLICAS, below["act"]))
-                    below["fused"] += x.C
-                elif (below_in and self.options.fuse_bn_reduce_stream and k_ == 1 and s == 1 and getattr(x, "bn_any", None) is not None and
-                      not x.bn_any["fused"] and x.bn_any["act"] == 1 and x.bn_any["cout"] == cin and x.bn_any["z"].ld % 4 == 0 and
-                      _lib.lib().fn["ep24_conv_kernel_for"](1, B, H, W, cin, seg.cout_pad, 1, 1, 0, 0) == 2):
-                    # d(x) is complete with this launch and is the dy of the unit below: its reduce pass rides on the rows being stored
-                    bl = x.bn_any
-                    zb, sv, ct = bl["z"], bl["save"], bl["cout"]
-                    self._b("conv1x1_dgrad_bnr_bf16", (dz, cout, ptr(home.wd, seg.wd_off), x.gptr(), x.gld, acc, B, H, W, cin, seg.cout_pad,
-                                                        zb.ptr(), zb.ld, ptr(sv, 0), ptr(sv, ct), ptr(flat, bl["gam"].off), ptr(flat, bl["bet"].off),
-                                                        bl["sum_g"], bl["sum_b"], 2 * ct, STATS_REPLICAS, 1))
-                    bl["fused"] += cin
-                    self.n_bnr_stream = getattr(self, "n_bnr_stream", 0) + 1
-                else:
-                    self._b("conv_dgrad_bf16", (dz, cout, ptr(home.wd, seg.wd_off), x.gptr(), x.gld, acc, B, H, W, cin,
-                                                seg.cout_pad, k_, s))
+                self._unit_dgrad(u, x_single, below_in)
 
         self._add_builder(build_bwd)
         return out
 
+    def _unit_fwd(self, u, bn2, bn_in):
+        """Forward launches of a unit: the conv (batch statistics in its epilogue), then BatchNorm + activation - or, where the
+        BatchNorm pass that made the input sits right in front and this conv streams its input through registers, that pass
+        absorbed into the conv (ep24_conv1x1_bnin_bf16)."""
+        x, z, out, seg, act, res_p, res_ld = u.x, u.z, u.out, u.seg, u.act, u.res_p, u.res_ld
+        B, H, W, cin, cout, k, s = x.B, x.H, x.W, u.cin, u.C, u.k, u.s
+        wf = ptr(self.home.wf, seg.wf_off)         # stem: master row [108] zero padded to the im2col width
+        if self.fold_bn_eval:
+            woff, coff = self._fold_w, self._fold_c
+            self._fold_w += cout * seg.taps * seg.cin_pad
+            self._fold_c += cout
+            self._fold_units.append((seg, u.gam, u.bet, u.bn, woff, coff))
+            fw, fb = (lambda: self.fold_w.data_ptr() + 2 * woff), (lambda: self.fold_b.data_ptr() + 4 * coff)
+            if u.focus:
+                assert res_p is None
+                ev_conv = ("stem_conv_fwd_infer_bf16", (x.ptr(), fw, seg.cin_pad, fb, act, out.ptr(), out.ld, B, H, W, cout))
+            else:
+                ev_conv = ("conv_fwd_infer_bf16", (x.ptr(), x.ld, fw, fb, act, res_p, res_ld, out.ptr(), out.ld, B, H, W, cin, cout, k, s))
+        elif u.focus:
+            ev_conv = ("stem_conv_fwd_bf16", (x.ptr(), wf, seg.cin_pad, z.ptr(), z.ld, None, 1, B, H, W, cout))
+        else:
+            ev_conv = ("conv_fwd_bf16", (x.ptr(), x.ld, wf, z.ptr(), z.ld, 0, 0, 0, None, None, 1, B, H, W, cin, cout, k, s))
+        u.xf_ok = (not u.stem and k == 1 and s == 1 and act == 1 and cout % 8 == 0 and
+                   _lib.lib().fn["ep24_conv1x1_xf_ok"](B, H, W, cin, cout) == 1)       # a shape of the transformed-A streaming kernel
+        prev = getattr(x, "_bnf", None) if bn_in and self.options.fuse_bn_stream and u.xf_ok else None
+        if prev is not None and prev[0] == len(self.fwd) - 1 and self.fwd[-1][0] == "bn_act_fwd" and prev[1].act == 1:
+            # The BatchNorm pass that produced x is the launch just before this one and this unit streams x through registers: it makes
+            # x itself (same expressions, same stored bytes) - the pass leaves the training list; the eval list keeps its own entries.
+            p = prev[1]
+            assert (p.y, p.ldy, p.M, p.C) == (x.ptr(), x.ld, u.M, cin)
+            self.fwd.pop()
+            self.fwd.append(("conv1x1_bnin_bf16", tuple(p[:15]) + (p.eps, p.mom, 1, wf, z.ptr(), z.ld, u.stats, STATS_REPLICAS, B, H, W, cin, cout)))
+            self.fwd_eval.append(ev_conv)
+            self.n_bnin += 1
+        elif u.focus:
+            self._f("stem_conv_fwd_bf16", x.ptr(), wf, seg.cin_pad, z.ptr(), z.ld, u.stats, STATS_REPLICAS, B, H, W, cout, ev=ev_conv)
+        else:
+            self._f("conv_fwd_bf16", x.ptr(), x.ld, wf, z.ptr(), z.ld, 0, 0, 0, None, u.stats, STATS_REPLICAS, B, H, W, cin, cout, k, s, ev=ev_conv)
+        p = self._bn_fwd(u.bn, u, z.ptr(), z.ld, u.stats, res_p, res_ld, bn2, infer=not self.fold_bn_eval)
+        out._bnf = (len(self.fwd) - 1, p)           # where this output's BatchNorm pass sits (a consumer with bn_in may absorb it)
 
-    def _unit_f32(self, mod, conv, bn, seg, gam, bet, x, z, out, residual, res_p, res_ld, k, s, act, save, sums):
+    def _unit_bn_bwd(self, u):
+        """BatchNorm backward of a unit: dy -> dz and the gamma / beta gradients.  One fused launch (PlanOptions.fuse_bn_bwd), or the
+        reduce pass (unless a consumer's input-gradient epilogue has produced the two sums) and then the apply pass - which, for a 1x1
+        unit of the streaming kernel, is one launch with the input gradient (PlanOptions.fuse_bn_dgrad, ep24_conv1x1_dgrad_bnbwd_bf16:
+        dz is made on the way to the MFMAs and stored for the weight gradient).  -> True when that launch made the input gradient."""
+        x, seg, cout = u.x, u.seg, u.C
+        assert u.fused in (0, cout), "BatchNorm-backward sums fused for a part of the channels only"
+        if u.bar is not None and not u.fused:
+            self._bn_bwd_apply(u, u.dz, cout, "bn_act_bwd_fused", (u.bar,))
+            return False
+        if not u.fused:
+            self._bn_bwd_reduce(u)
+        if u.xf_ok and self.options.fuse_bn_dgrad and x.needs_grad and not u.fused and seg.cout_pad == cout:
+            acc = x.gwrite()
+            gflat = self.home.gflat
+            self._b("conv1x1_dgrad_bnbwd_bf16", self._bn_bwd_args(u) + (
+                ptr(gflat, u.gam.off), ptr(gflat, u.bet.off), u.dz, cout, u.act, STATS_REPLICAS,
+                ptr(self.home.wd, seg.wd_off), x.gptr(), x.gld, acc, x.B, x.H, x.W, u.cin, cout), writes=(u.gam, u.bet))
+            self.n_bnbwd += 1
+            return True
+        self._bn_bwd_apply(u, u.dz, cout)
+        return False
+
+    def _unit_wgrad(self, u):
+        """Weight gradient of a unit: grouped with the other layers of its tile class, or a slab launch of its own (the stem, the
+        tail of backward, plans without grouping)."""
+        x, seg, cout = u.x, u.seg, u.C
+        B, H, W = x.B, x.H, x.W
+        if self.options.group_wgrad and not u.focus and not self._wg_tail and not (self.options.conv_kernel_opts & 0x100):
+            # csrc/conv_wgrad.hip wgrad_group_kernel; its slab is allotted when the group is launched (the split count is the group's)
+            self._pend_wgrad(dict(x=x.ptr, ld_x=x.ld, dz=u.dz, ld_dy=cout, ld_dw=seg.taps * seg.cin, cout_valid=cout, cin_valid=seg.cin,
+                                  B=B, H=H, W=W, cin=u.cin, cout=cout, k=u.k, s=u.s, seg=seg, idx=u.idx))
+            if len(self._pending_reduce) >= WGRAD_REDUCE_GROUP:
+                self._flush_reduce()
+        elif u.focus:
+            self._layer_wgrad("stem_conv_wgrad_slab_bf16", seg, _lib.lib().fn["ep24_stem_conv_wgrad_splits"](B, H, W, cout), u.idx,
+                              lambda slab_p, floats: (x.ptr(), u.dz, cout, slab_p, floats, B, H, W, cout))
+        else:
+            self._layer_wgrad("conv_wgrad_slab_bf16", seg, self._wsplits(B, H, W, u.cin, cout, u.k, u.s), u.idx,
+                              self._conv_wgrad_args(seg, x, u.dz, cout, u.cin, cout, u.k, u.s))
+
+    def _unit_dgrad(self, u, x_single, below_in):
+        """Input gradient of a unit.  Where d(x) is complete with this launch and IS the dy of the unit below, that unit's
+        BatchNorm-backward sums ride on the rows being stored (ep24_conv_dgrad_bnr_bf16: 3x3 stride 1 and the only consumer,
+        PlanOptions.fuse_bn_reduce; ep24_conv1x1_dgrad_bnr_bf16: the streaming 1x1 kernel, PlanOptions.fuse_bn_reduce_stream)."""
+        x, seg, cout, cin, k, s = u.x, u.seg, u.C, u.cin, u.k, u.s
+        B, H, W = x.B, x.H, x.W
+        flat, wd = self.home.flat, ptr(self.home.wd, seg.wd_off)
+        acc = x.gwrite()
+        below = getattr(x, "bn_info", None) if x_single else None
+        any_ = getattr(x, "bn_any", None) if below_in else None
+        if (below is not None and not acc and k == 3 and s == 1 and self.options.fuse_bn_reduce and x._alias is None and
+                x.C % 8 == 0 and x.gld % 8 == 0 and below.z.ld % 8 == 0):
+            o, ct = x.bn_c0, below.C
+            self._b("conv_dgrad_bnr_bf16", (u.dz, cout, wd, x.gptr(), x.gld, B, H, W, cin, seg.cout_pad, k,
+                                            below.z.ptr() + 2 * o, below.z.ld, ptr(below.save, o), ptr(below.save, ct + o),
+                                            ptr(flat, below.gam.off + o), ptr(flat, below.bet.off + o),
+                                            (lambda f=below.sum_g: f() + 8 * o), (lambda f=below.sum_b: f() + 8 * o),
+                                            2 * ct, STATS_REPLICAS, below.act))
+            below.fused += x.C
+        elif (any_ is not None and self.options.fuse_bn_reduce_stream and k == 1 and s == 1 and
+              not any_.fused and any_.act == 1 and any_.C == cin and any_.z.ld % 4 == 0 and
+              _lib.lib().fn["ep24_conv_kernel_for"](1, B, H, W, cin, seg.cout_pad, 1, 1, 0, 0) == 2):
+            ct = any_.C
+            self._b("conv1x1_dgrad_bnr_bf16", (u.dz, cout, wd, x.gptr(), x.gld, acc, B, H, W, cin, seg.cout_pad,
+                                                any_.z.ptr(), any_.z.ld, ptr(any_.save, 0), ptr(any_.save, ct), ptr(flat, any_.gam.off),
+                                                ptr(flat, any_.bet.off), any_.sum_g, any_.sum_b, 2 * ct, STATS_REPLICAS, 1))
+            any_.fused += cin
+            self.n_bnr_stream += 1
+        else:
+            self._b("conv_dgrad_bf16", (u.dz, cout, wd, x.gptr(), x.gld, acc, B, H, W, cin, seg.cout_pad, k, s))
+
+    def _unit_f32(self, u, bn2):
         """The unit in the fp32 parity mode: same buffers and gradient bookkeeping, weights read in place from the fp32
         master ([Cout][T][Cin] = element (co, t, ci) at co*T*Cin + t*Cin + ci), everything on one lane."""
-        home = self.home
-        flat, gflat = home.flat, home.gflat
+        x, z, out, seg, gam, bet, bn, act, save, k, s = u.x, u.z, u.out, u.seg, u.gam, u.bet, u.bn, u.act, u.save, u.k, u.s
+        flat, gflat = self.home.flat, self.home.gflat
         B, H, W = x.B, x.H, x.W
         cin, cout, T = seg.cin, seg.cout, seg.taps     # stem: cin = 108 real columns of the 112-wide rows, one tap
-        M = out.M
+        M = u.M
         wco, wt = T * cin, cin
         w_p, gw_p = ptr(flat, seg.off), ptr(gflat, seg.off)
+        if bn2 is not None:
+            self._f("incr_i64", ptr(bn2.num_batches_tracked), ev=False)
         self._f("f32_conv", x.ptr(), x.ld, w_p, wco, wt, z.ptr(), z.ld, 0, 0, None, 0, B, H, W, cin, cout, k, s, 0, ev=False)
         self._f("f32_bn_act_fwd", z.ptr(), z.ld, ptr(flat, gam.off), ptr(flat, bet.off), ptr(bn.running_mean), ptr(bn.running_var),
-                ptr(bn.num_batches_tracked), ptr(save), out.ptr(), out.ld, res_p, res_ld, M, cout, float(bn.eps), float(bn.momentum),
+                ptr(bn.num_batches_tracked), ptr(save), out.ptr(), out.ld, u.res_p, u.res_ld, M, cout, float(bn.eps), float(bn.momentum),
                 act, ev=False)
-        if residual is not None:
-            residual.alias_grad(out)
-        self.unit_acts[mod if mod is not None else conv] = (x, z, out)
 
         def build_bwd():
             assert out.gready(), "activation without a gradient producer"
-            self._bwd_units += 1
-            dzoff = self._dz_elems
-            self._dz_elems += M * cout
-            dz = (lambda dzoff=dzoff: self.dzbuf.data_ptr() + 4 * dzoff)
-            self._b("f32_bn_act_bwd", (out.gptr(), out.gld, z.ptr(), z.ld, ptr(save), ptr(flat, gam.off), ptr(flat, bet.off), sums,
-                                       ptr(gflat, gam.off), ptr(gflat, bet.off), dz, cout, M, cout, act), writes=(gam, bet), reads=out)
+            dz = self._bwd_slot(M * cout)[1]
+            self._b("f32_bn_act_bwd", (out.gptr(), out.gld, z.ptr(), z.ld, ptr(save), ptr(flat, gam.off), ptr(flat, bet.off), u.sum_g,
+                                       ptr(gflat, gam.off), ptr(gflat, bet.off), dz, cout, M, cout, act), writes=(gam, bet))
             self._b("f32_conv_wgrad", (x.ptr(), x.ld, dz, cout, gw_p, wco, wt, B, H, W, cin, cout, k, s), writes=(seg,))
             if x.needs_grad:
                 acc = x.gwrite()
@@ -1291,7 +1326,6 @@ class Engine:
 
         def build_bwd():
             assert y.gready(), "activation without a gradient producer"
-            _PENDING_GW.append(y.gregion())
             self._b("relu_bwd", (y.gptr(), y.gld, y.ptr(), y.ld, y.M, y.C))
 
         self._add_builder(build_bwd)
@@ -1299,31 +1333,22 @@ class Engine:
 
     def maxpool3s2(self, x, out=None):
         """nn.MaxPool2d(3, 2, 1) (darknet.py:303)."""
-        OH, OW = (x.H - 1) // 2 + 1, (x.W - 1) // 2 + 1
-        y = self.new_act(x.C, OH, OW) if out is None else out
-        assert (y.H, y.W, y.C) == (OH, OW, x.C)
-        idx = torch.zeros(y.M * x.C, dtype=torch.uint8, device=self.dev)
-        self._f("maxpool3s2_fwd", x.ptr(), x.ld, y.ptr(), y.ld, ptr(idx), x.B, x.H, x.W, x.C)
-
-        def build_bwd():
-            assert y.gready()
-            acc = x.gwrite()
-            self._b("maxpool3s2_bwd", (y.gptr(), y.gld, ptr(idx), x.gptr(), x.gld, acc, x.B, x.H, x.W, x.C))
-
-        self._add_builder(build_bwd)
-        return y
+        return self._maxpool("maxpool3s2", x, (x.H - 1) // 2 + 1, (x.W - 1) // 2 + 1, out)
 
     def maxpool2(self, x, out=None):
         """nn.MaxPool2d(kernel_size=2, stride=2) (darknet.py:481)."""
-        y = self.new_act(x.C, x.H // 2, x.W // 2) if out is None else out
-        assert (y.H, y.W, y.C) == (x.H // 2, x.W // 2, x.C)
+        return self._maxpool("maxpool2", x, x.H // 2, x.W // 2, out)
+
+    def _maxpool(self, name, x, OH, OW, out):
+        y = self.new_act(x.C, OH, OW) if out is None else out
+        assert (y.H, y.W, y.C) == (OH, OW, x.C)
         idx = torch.zeros(y.M * x.C, dtype=torch.uint8, device=self.dev)
-        self._f("maxpool2_fwd", x.ptr(), x.ld, y.ptr(), y.ld, ptr(idx), x.B, x.H, x.W, x.C)
+        self._f(name + "_fwd", x.ptr(), x.ld, y.ptr(), y.ld, ptr(idx), x.B, x.H, x.W, x.C)
 
         def build_bwd():
             assert y.gready()
             acc = x.gwrite()
-            self._b("maxpool2_bwd", (y.gptr(), y.gld, ptr(idx), x.gptr(), x.gld, acc, x.B, x.H, x.W, x.C))
+            self._b(name + "_bwd", (y.gptr(), y.gld, ptr(idx), x.gptr(), x.gld, acc, x.B, x.H, x.W, x.C))
 
         self._add_builder(build_bwd)
         return y
@@ -1390,20 +1415,10 @@ class Engine:
 
         def build_bwd():
             assert out.gready(), "activation without a gradient producer"
-            splits = self._wsplits(B, H, W, cin, cout, k, s)
-            soff = self._slab_floats
-            self._slab_floats += splits * seg.numel
-            idx = self._bwd_units
-            self._bwd_units += 1
             # the chunk of the concatenation's gradient this conv owns is final here (every later consumer has run) and
             # nothing writes those columns again, so the weight-gradient lane can read it in place
-            self._b("@side_wait_main", ())
-            self._b("side:conv_wgrad_slab_bf16", (x.ptr(), x.ld, out.gptr(), out.gld, (lambda soff=soff: self.slab.data_ptr() + 4 * soff),
-                                                  splits * seg.numel, seg.taps * seg.cin, cout, seg.cin, B, H, W, cin, cout, k, s))
-            self._b("@side_record", (idx,))
-            self._pending_reduce.append((seg, splits, soff))
-            if len(self._pending_reduce) >= WGRAD_REDUCE_GROUP:
-                self._flush_reduce()
+            self._layer_wgrad("conv_wgrad_slab_bf16", seg, self._wsplits(B, H, W, cin, cout, k, s), self._bwd_slot()[0],
+                              self._conv_wgrad_args(seg, x, out.gptr(), out.gld, cin, cout, k, s))
             if x.needs_grad:
                 acc = x.gwrite()
                 self._b("conv_dgrad_bf16", (out.gptr(), out.gld, ptr(home.wd, seg.wd_off), x.gptr(), x.gld, acc, B, H, W, cin,
@@ -1416,30 +1431,21 @@ class Engine:
         """Pre-activation BatchNorm + ReLU over ``x`` (a prefix of a block's concatenation): the batch statistics are the
         block's (``bstats``, one entry per channel of the whole concatenation, filled as chunks are produced); the layer
         gathers its prefix.  In backward the input gradient ACCUMULATES into the concatenation's gradient."""
-        home = self.home
-        gam, bet = home.by_param[bn.weight], home.by_param[bn.bias]
-        C, M = x.C, x.M
+        home, C = self.home, x.C
         a = self.new_act(C, x.H, x.W)
         self.pre_bn_inputs[bn] = x
         lstats = self._stats_slot(C)
-        save = torch.zeros(2 * C, dtype=torch.float32, device=self.dev)
-        sum_g, sum_b = self._sums_slot(C)
-        flat, gflat = home.flat, home.gflat
+        u = Unit(x=x, z=x, out=a, gam=home.by_param[bn.weight], bet=home.by_param[bn.bias], act=2, M=x.M, C=C,
+                 save=torch.zeros(2 * C, dtype=torch.float32, device=self.dev))
+        u.sum_g, u.sum_b = self._sums_slot(C)
         self._f("stats_gather", bstats, ld_stats, lstats, C, STATS_REPLICAS, ev=False)
-        self._f("bn_act_fwd", x.ptr(), x.ld, lstats, STATS_REPLICAS, ptr(flat, gam.off), ptr(flat, bet.off), ptr(bn.running_mean),
-                ptr(bn.running_var), ptr(bn.num_batches_tracked), None, ptr(save), a.ptr(), a.ld, None, 0, M, C, float(bn.eps),
-                float(bn.momentum), 2,
-                ev=("bn_act_infer", (x.ptr(), x.ld, ptr(flat, gam.off), ptr(flat, bet.off), ptr(bn.running_mean),
-                                     ptr(bn.running_var), a.ptr(), a.ld, None, 0, M, C, float(bn.eps), 2)))
+        self._bn_fwd(bn, u, x.ptr(), x.ld, lstats)
 
         def build_bwd():
             assert a.gready(), "activation without a gradient producer"
             acc = x.gwrite()
-            self._b("bn_act_bwd_reduce", (a.gptr(), a.gld, x.ptr(), x.ld, ptr(save), ptr(flat, gam.off), ptr(flat, bet.off),
-                                          sum_g, sum_b, M, C, 2, STATS_REPLICAS), reads=a)
-            self._b("bn_act_bwd_apply_acc" if acc else "bn_act_bwd_apply",
-                    (a.gptr(), a.gld, x.ptr(), x.ld, ptr(save), ptr(flat, gam.off), ptr(flat, bet.off), sum_g, sum_b,
-                     ptr(gflat, gam.off), ptr(gflat, bet.off), x.gptr(), x.gld, M, C, 2, STATS_REPLICAS), writes=(gam, bet))
+            self._bn_bwd_reduce(u)
+            self._bn_bwd_apply(u, x.gptr(), x.gld, "bn_act_bwd_apply_acc" if acc else "bn_act_bwd_apply")
 
         self._add_builder(build_bwd)
         return a
@@ -1452,7 +1458,6 @@ class Engine:
 
         def build_bwd():
             assert x.gready()
-            _PENDING_GW.append(x.gregion())
             self._b("chanscale", (x.gptr(), x.gld, ptr(keep), x.B, x.H * x.W, x.C))
 
         self._add_builder(build_bwd)
@@ -1507,19 +1512,11 @@ class Engine:
 
     def avgpool2(self, x, y):
         """nn.AvgPool2d(2, 2) into ``y`` (the head of the next block's concatenation)."""
-        self._f("avgpool2_fwd", x.ptr(), x.ld, y.ptr(), y.ld, x.B, x.H, x.W, x.C)
-
-        def build_bwd():
-            assert y.gready()
-            acc = x.gwrite()
-            self._b("avgpool2_bwd", (y.gptr(), y.gld, x.gptr(), x.gld, acc, x.B, x.H, x.W, x.C))
-
-        self._add_builder(build_bwd)
-        return y
+        return self._resample("avgpool2", x, y)
 
     def draw_dropout(self):
         """New Dropout2d keep factors for the next training forward (torch's generator on the device: no host sync)."""
-        if getattr(self, "drop_keep", None) is not None and not getattr(self, "fixed_dropout", False):
+        if self.drop_keep is not None and not self.fixed_dropout:
             self.drop_keep.bernoulli_(1.0 - self.drop_p).div_(1.0 - self.drop_p)
 
     def csp_merged(self, mod, x, out=None):
@@ -1575,15 +1572,19 @@ class Engine:
         return self.unit(mod.conv2, cat)
 
     def up2(self, x, y):
-        pre = "f32_" if self.f32 else ""
-        self._f(pre + "upsample2_fwd", x.ptr(), x.ld, y.ptr(), y.ld, x.B, x.H, x.W, x.C, ev=False if self.f32 else None)
+        self._resample("f32_upsample2" if self.f32 else "upsample2", x, y, ev=False if self.f32 else None)
+
+    def _resample(self, name, x, y, ev=None):
+        """``x`` -> ``y`` by ep24_<name>_fwd; ep24_<name>_bwd overwrites or accumulates d(x)."""
+        self._f(name + "_fwd", x.ptr(), x.ld, y.ptr(), y.ld, x.B, x.H, x.W, x.C, ev=ev)
 
         def build_bwd():
             assert y.gready()
             acc = x.gwrite()
-            self._b(pre + "upsample2_bwd", (y.gptr(), y.gld, x.gptr(), x.gld, acc, x.B, x.H, x.W, x.C))
+            self._b(name + "_bwd", (y.gptr(), y.gld, x.gptr(), x.gld, acc, x.B, x.H, x.W, x.C))
 
         self._add_builder(build_bwd)
+        return y
 
     def head_level(self, head, k, feat, a0):
         """stem -> {cls branch -> cls_preds, reg branch -> reg_preds + obj_preds} -> decode (yolo_head_24p.py:150-189)."""
@@ -1633,27 +1634,20 @@ class Engine:
             # bias and weight gradients of the prediction convs: side lane, slab partials folded by the next reduce launch
             fn = _lib.lib().fn
 
-            def emit_pred_grads():
+            def emit_pred_grads():                    # four launches behind one wait; the reduce that folds them comes with a later layer's
                 self._b("@side_wait_main", ())
                 for dsrc, ld_d, bseg, n in ((d_ro, 32, ro_b, 27), (d_cl, ldc, cl_b, C)):
                     sp = fn["ep24_colsum_splits"](M)
-                    soff = self._slab_floats
-                    self._slab_floats += sp * n + (-(sp * n)) % 4
-                    self._b("side:colsum_slab", (ptr(dsrc), ld_d, (lambda soff=soff: self.slab.data_ptr() + 4 * soff), M, n))
-                    self._pending_reduce.append((bseg, sp, soff))
-                for feat_in, dsrc, ld_d, wseg, n, npad in ((rf, d_ro, 32, ro_seg, 27, 32), (cf, d_cl, ldc, cl_seg, C, ldc)):
+                    soff, slab_p = self._slab_alloc(sp * n + (-(sp * n)) % 4)
+                    self._b("side:colsum_slab", (ptr(dsrc), ld_d, slab_p, M, n))
+                    self._pend_reduce(bseg, sp, soff, flush=False)
+                for feat_in, dsrc, ld_d, wseg, npad in ((rf, d_ro, 32, ro_seg, 32), (cf, d_cl, ldc, cl_seg, ldc)):
                     sp = self._wsplits(B, H, W, hch, npad, 1, 1)
-                    soff = self._slab_floats
-                    self._slab_floats += sp * wseg.numel
-                    self._b("side:conv_wgrad_slab_bf16", (feat_in.ptr(), feat_in.ld, ptr(dsrc), ld_d,
-                                                          (lambda soff=soff: self.slab.data_ptr() + 4 * soff), sp * wseg.numel, hch, n, hch,
-                                                          B, H, W, hch, npad, 1, 1))
-                    self._pending_reduce.append((wseg, sp, soff))
+                    soff, slab_p = self._slab_alloc(sp * wseg.numel)
+                    self._b("side:conv_wgrad_slab_bf16", self._conv_wgrad_args(wseg, feat_in, ptr(dsrc), ld_d, hch, npad, 1, 1)(slab_p, sp * wseg.numel))
+                    self._pend_reduce(wseg, sp, soff, flush=False)
 
-            if self._force_side:
-                self._deferred.append(emit_pred_grads)
-            else:
-                emit_pred_grads()
+            self._side_later(emit_pred_grads)
             self._b("conv_dgrad_bf16", (ptr(d_ro), 32, ptr(home.wd, ro_seg.wd_off), rf.gptr(), rf.gld, rf.gwrite(), B, H,
                                         W, hch, 32, 1, 1))
             self._b("conv_dgrad_bf16", (ptr(d_cl), ldc, ptr(home.wd, cl_seg.wd_off), cf.gptr(), cf.gld, cf.gwrite(), B, H,
@@ -1688,7 +1682,7 @@ class Engine:
         self._add_builder(build_bwd)
 
     # ---- execution ----------------------------------------------------------------------------------
-    def _run(self, lst):
+    def _run(self, lst, skip_decode=False):
         """Launch a list on the current stream.  Entries named ``side:<fn>`` go to a second stream; the control
         entries ``@side_wait_main`` / ``@side_record(k)`` / ``@main_wait_side(k)`` order the two with events.  The
         call returns with the side stream joined.  Under hipGraph capture everything stays on the capturing stream:
@@ -1702,7 +1696,6 @@ class Engine:
         if self._side is None:
             self._side = torch.cuda.Stream(device=self.dev)
         side, s_side = self._side, self._side.cuda_stream
-        fn = _lib.lib().fn
         events, used_side = {}, False
         for name, args in lst:
             if name[0] == "@":
@@ -1734,13 +1727,18 @@ class Engine:
                 if lanes:
                     s = s_side
                     used_side = True
-            if name == "head_decode_bwd" and self.skip_decode_bwd:
-                continue
-            rc = fn["ep24_" + name](*[a.get() if isinstance(a, Dyn) else a for a in args], s)
-            if rc != 0:
-                raise _lib.Ep24Error("ep24_%s failed (%d): %s" % (name, rc, _lib.lib().last_error()))
+            self._launch(name, args, s, skip_decode)
         if used_side:
             main.wait_stream(side)
+
+    def _launch(self, name, args, stream, skip_decode):
+        """One entry of a launch list on ``stream``.  ``skip_decode``: the caller's loss has written the rows the prediction convs'
+        backward reads itself (ep24_loss_grad_decode), so the plan's head_decode_bwd entries do not run."""
+        if name == "head_decode_bwd" and skip_decode:
+            return
+        rc = _lib.lib().fn["ep24_" + name](*[a.get() if isinstance(a, Dyn) else a for a in args], stream)
+        if rc != 0:
+            raise _lib.Ep24Error("ep24_%s failed (%d): %s" % (name, rc, _lib.lib().last_error()))
 
     def lane_lists(self, lo, hi):
         """Backward entries [lo, hi) split into the main lane and the weight-gradient lane (control entries dropped).
@@ -1755,21 +1753,15 @@ class Engine:
                 main.append((name, args))
         return main, side
 
-    def run_lane(self, lst):
+    def run_lane(self, lst, skip_decode=False):
         """Launch plain entries on the current stream (capturable)."""
         s = stream_ptr()
-        fn = _lib.lib().fn
         for name, args in lst:
-            if name == "head_decode_bwd" and self.skip_decode_bwd:
-                continue
-            rc = fn["ep24_" + name](*[a.get() if isinstance(a, Dyn) else a for a in args], s)
-            if rc != 0:
-                raise _lib.Ep24Error("ep24_%s failed (%d): %s" % (name, rc, _lib.lib().last_error()))
+            self._launch(name, args, s, skip_decode)
 
     def decode_levels(self):
         """HOST table for ep24_loss_grad_decode: per head level (cells per image, the stride's float32 bits, d_regobj, d_cls)."""
-        import struct
-        if getattr(self, "_decode_levels", None) is None:
+        if self._decode_levels is None:
             rows = [[hw, struct.unpack("<I", struct.pack("<f", float(s)))[0], d_ro.data_ptr(), d_cl.data_ptr()] for hw, s, d_ro, d_cl in self.head_grads]
             self._decode_levels = torch.tensor(rows, dtype=torch.int64)
         return self._decode_levels
@@ -1825,8 +1817,7 @@ class Engine:
         [B,A,26] the gradient of the L1 branch with respect to the raw regression outputs (or None)."""
         self.dyn["dout"] = dout.data_ptr()
         self.dyn["d_origin"] = None if d_origin is None else d_origin.data_ptr()
-        self.skip_decode_bwd = False              # the eager API hands over the dense gradient: the decode backward launches run
-        self._run(self.bwd)
+        self._run(self.bwd)                       # the eager API hands over the dense gradient: the decode backward launches run
 
     # ---- nn.Module / autograd entry -----------------------------------------------------------------
     def run_module_forward(self, x, train):

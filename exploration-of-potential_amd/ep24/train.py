@@ -146,7 +146,9 @@ class TrainStep:
         self.st = torch.cat(eng.exp_strides, 1)[0].contiguous()
         self.labels = torch.zeros(eng.B, 50, 51, dtype=torch.float32, device=eng.dev)
         self.graphs = None
-        self._side = None
+        self._side = self._side2 = None
+        self._cost_done = ()                             # anchor ranges whose SimOTA cost rows a forward lane has already written
+        self.probe = None                                # tools/fwd_lanes_probe.py: a dict that collects timed events at the lane boundaries
         self.use_graph = use_graph
         # backward runs on two lanes (main: BN backward / dgrad / glue, side: weight gradients).  graph_backward=True
         # replays each lane as a chain of captured segments (no launch gaps: 28.7 ms/step at YOLOX-l / B=20);
@@ -212,7 +214,7 @@ class TrainStep:
     # that leave most of the chip idle).  Three graphs, two events, no cross-stream edge inside a graph.
     def _fwd_split(self):
         eng = self.eng
-        if getattr(eng, "fwd_head0", None) is None or not self.parallel_forward:
+        if eng.fwd_head0 is None or not self.parallel_forward:
             return None
         lo, hi = eng.fwd_head0
         fork = eng.fwd_fork
@@ -220,7 +222,7 @@ class TrainStep:
         # the default since round 5, behind head level 0 on the second lane.  Timed events in a plain run (profiles/r05_fwd_lanes.txt)
         # showed the main lane - rest of the neck + head levels 1, 2 - finishing 0.84 ms AFTER the level-0 head, the opposite of what
         # the profiler's trace had suggested for two rounds.
-        if (self.forward_lanes >= 3 or self.eng.options.head1_side) and getattr(eng, "fwd_head1", None) is not None:
+        if (self.forward_lanes >= 3 or self.eng.options.head1_side) and eng.fwd_head1 is not None:
             f1, (lo1, hi1) = eng.fwd_fork1, eng.fwd_head1
             return eng.fwd[:fork], eng.fwd[fork:f1], eng.fwd[lo:hi], eng.fwd[f1:lo] + eng.fwd[hi1:], eng.fwd[lo1:hi1]
         return eng.fwd[:fork], eng.fwd[fork:lo] + eng.fwd[hi:], eng.fwd[lo:hi]
@@ -250,26 +252,34 @@ class TrainStep:
         self.home.pack_rest_forward()
         eng.run_lane(self._fwd_split()[0])
 
-    def _loss_grad(self, origin):
-        """The loss gradient.  Default (round 5): fused with the head's decode backward - the rows the prediction convs' backward reads
-        are written directly (ep24_loss_grad_decode) and the plan's head_decode_bwd entries are skipped; with the L1 branch, or
-        PlanOptions(fuse_loss_decode=False), the dense fp32 gradient + the three head_decode_bwd launches."""
+    def _fused_decode(self):
+        """True (the default, round 5): the loss gradient is fused with the head's decode backward - the rows the prediction convs'
+        backward reads are written directly (ep24_loss_grad_decode) and the plan's head_decode_bwd entries are skipped.  False - with
+        the L1 branch, or PlanOptions(fuse_loss_decode=False): the dense fp32 gradient + the three head_decode_bwd launches.  Loss and
+        backward of one step must agree on it; graphs hold the choice they were captured with (set_use_l1 drops them)."""
         eng = self.eng
-        fused = bool(eng.options.fuse_loss_decode) and not self.use_l1 and len(eng.head_grads) > 0
-        eng.skip_decode_bwd = fused
+        return bool(eng.options.fuse_loss_decode) and not self.use_l1 and len(eng.head_grads) > 0
+
+    def _backward_inputs(self):
+        """Points the plan's run-time arguments at this step's loss gradient (an eager Engine.backward() in between points them at
+        its caller's tensors) -> whether the head_decode_bwd entries are skipped."""
+        self.eng.dyn["dout"] = self.ws.dout.data_ptr()
+        self.eng.dyn["d_origin"] = self.ws.l1_grad_buffer().data_ptr() if self.use_l1 else None
+        return self._fused_decode()
+
+    def _loss_grad(self, origin, fused):
+        eng = self.eng
         if fused:
             eloss.loss_grad_decode(self.ws, eng.outputs, self.labels, eng.decode_levels())
         else:
             eloss.loss_grad(self.ws, eng.outputs, self.labels, None, origin, (self.xs, self.ys, self.st))
-        eng.dyn["dout"] = self.ws.dout.data_ptr()
-        eng.dyn["d_origin"] = self.ws.d_origin.data_ptr() if self.use_l1 else None
 
     def _phase_loss(self):
         eng = self.eng
         origin = eng.origin if self.use_l1 else None
         eloss.assign_and_reduce(self.ws, eng.outputs, self.labels, self.xs, self.ys, self.st, self.state, origin, candidates_done=True,
-                                cost_done=getattr(self, "_cost_done", ()))
-        self._loss_grad(origin)
+                                cost_done=self._cost_done)
+        self._loss_grad(origin, self._fused_decode())
 
     def _phase_forward(self):
         eng = self.eng
@@ -277,11 +287,11 @@ class TrainStep:
         eng.forward()
         origin = eng.origin if self.use_l1 else None
         eloss.assign_and_reduce(self.ws, eng.outputs, self.labels, self.xs, self.ys, self.st, self.state, origin)
-        self._loss_grad(origin)
+        self._loss_grad(origin, self._fused_decode())
 
     def _phase_backward(self, lo, hi):
         eng = self.eng
-        eng._run(eng.bwd[lo:hi])
+        eng._run(eng.bwd[lo:hi], self._backward_inputs())
 
     def _phase_update(self, lo=0, hi=None, last=True):
         self.home.sgd_hp(self.hp, self.ema_home, lo, hi, last, decay=self.weight_decay != 0.0)
@@ -350,7 +360,7 @@ class TrainStep:
             rc = self.reducer.cuts(self.eng)
             cuts |= set(rc)
             ready = {c: i for i, c in enumerate(rc[1:])}          # cut index -> reducer segment that ends there
-        if getattr(self.eng, "bwd_tail_cut", None):            # the reduce launch in front of the last unit closes a segment:
+        if self.eng.bwd_tail_cut:                              # the reduce launch in front of the last unit closes a segment:
             cuts.add(self.eng.bwd_tail_cut)                    # the side lane runs it while the main lane does that unit's BatchNorm
         if self.eng.options.tail_cuts:
             # At the END of backward what the side lane still holds is exposed.  A weight gradient waits for the main lane to finish the
@@ -425,7 +435,7 @@ class TrainStep:
             self.g_fwd = (capture(self._phase_forward_head),) + tuple(lanes) + (capture(self._phase_loss),)
             if self._side is None:
                 self._side = torch.cuda.Stream(device=eng.dev)
-            if len(split) == 5 and getattr(self, "_side2", None) is None:
+            if len(split) == 5 and self._side2 is None:
                 self._side2 = torch.cuda.Stream(device=eng.dev) if self.forward_lanes >= 3 else self._side
         self.g_upd = capture(self._phase_update)
         self.g_upd_early = None
@@ -436,16 +446,17 @@ class TrainStep:
             # which starts a segment when the main lane has finished it - one event per segment, none inside a graph
             segs, ready = self._segments()
             self.g_bwd = []
+            skip = self._backward_inputs()
             early = self._early_update_cut(segs)
             chunks, upd_hi = self._update_chunks(segs, early[1]) if early is not None and self.chunked_update else ({}, None)
             self.update_chunks = dict(chunks)
             for si, (lo, hi) in enumerate(segs):
                 main, side = eng.lane_lists(lo, hi)
-                gm = capture(lambda: eng.run_lane(main)) if main else None
+                gm = capture(lambda: eng.run_lane(main, skip)) if main else None
                 piece = chunks.get(si)
 
                 def side_work(side=side, piece=piece):
-                    eng.run_lane(side)
+                    eng.run_lane(side, skip)
                     if piece is not None:                     # the parameters whose gradients this segment has completed
                         self._phase_update(piece[0], piece[1], False)
 
@@ -496,13 +507,7 @@ class TrainStep:
         if isinstance(self.g_fwd, tuple) and len(self.g_fwd) == 6:
             g1, g_main_a, g_side, g_main_b, g_side2, g_loss = self.g_fwd
             main, side, side2 = torch.cuda.current_stream(), self._side, self._side2
-            probe = getattr(self, "probe", None)      # tools/fwd_lanes_probe.py: timed events at the lane boundaries (outside a profiler)
-
-            def mark(name, stream):
-                if probe is not None:
-                    e = torch.cuda.Event(enable_timing=True)
-                    e.record(stream)
-                    probe[name] = e
+            mark = self._mark
             mark("start", main)
             g1.replay()
             mark("fork", main)
@@ -534,13 +539,7 @@ class TrainStep:
         elif isinstance(self.g_fwd, tuple):
             g1, g_main, g_side, g_loss = self.g_fwd
             main, side = torch.cuda.current_stream(), self._side
-            probe = getattr(self, "probe", None)      # tools/fwd_lanes_probe.py: timed events at the lane boundaries (outside a profiler)
-
-            def mark(name, stream):
-                if probe is not None:
-                    e = torch.cuda.Event(enable_timing=True)
-                    e.record(stream)
-                    probe[name] = e
+            mark = self._mark
             mark("start", main)
             g1.replay()
             mark("fork", main)
@@ -577,13 +576,7 @@ class TrainStep:
             # the main lane's graph of segment i+1 is enqueued BEFORE the side lane's graph of segment i.
             pending, par_done = None, None
 
-            bprobe = getattr(self, "probe", None)
-
-            def bmark(key, stream):                          # tools/fwd_lanes_probe.py: where each lane is, segment by segment
-                if bprobe is not None:
-                    e = torch.cuda.Event(enable_timing=True)
-                    e.record(stream)
-                    bprobe.setdefault(key, []).append(e)
+            bmark = lambda key, stream: self._mark(key, stream, True)     # where each lane is, segment by segment
             bmark("bwd_main", main)
 
             def launch_side(p):
@@ -655,8 +648,15 @@ class TrainStep:
             self.g_upd_early[1].replay()                     # the parameters below the cut; finishes the step
         else:
             self.g_upd.replay()
-        if getattr(self, "probe", None) is not None:
-            e = torch.cuda.Event(enable_timing=True)
-            e.record(torch.cuda.current_stream())
-            self.probe["end"] = e
+        self._mark("end", torch.cuda.current_stream())
         return self.ws.result
+
+    def _mark(self, name, stream, many=False):
+        """A timed event on ``stream`` into ``self.probe`` (outside a profiler; ``many``: one per call, a list), if a probe is set."""
+        if self.probe is not None:
+            e = torch.cuda.Event(enable_timing=True)
+            e.record(stream)
+            if many:
+                self.probe.setdefault(name, []).append(e)
+            else:
+                self.probe[name] = e

@@ -433,6 +433,50 @@ def test_update_keeps_the_packed_forward_weights_current():
     assert home.wf_current and np.isfinite(l_half) and l_half != losses[-1]
     m.head.load_state_dict(m.head.state_dict())
     assert not home.wf_current
+    # ... and the eager update (Optimizer.step -> ParamHome.sgd), which writes the masters but not the packed copy
+    ts.step()
+    torch.cuda.synchronize()
+    assert home.wf_current
+    home.sgd(0.01, 0.9)
+    assert not home.wf_current
+    ts.step()
+    torch.cuda.synchronize()
+    want = fresh()
+    for seg in home.convs:
+        if seg not in home.pack_rest:
+            n = seg.cout * seg.taps * seg.cin_pad
+            assert torch.equal(home.wf[seg.wf_off:seg.wf_off + n], want[seg.wf_off:seg.wf_off + n]), seg.off
+
+
+@pytest.mark.parametrize("plan", ["", "fuse_loss_decode=0"])
+def test_decode_choice_survives_an_eager_backward(plan):
+    """Whether the loss writes the rows the prediction convs' backward reads itself (and the plan's head_decode_bwd entries are
+    skipped) belongs to the TrainStep, not to the engine: an eager Engine.backward() between two steps - which runs the decode
+    backward on its caller's dense gradient - must leave the next step's gradients bit-identical to the first step's.  Host-launched
+    backward lanes behind a captured forward + loss: the loss's choice is frozen in the graph, backward's is read at every step."""
+    from ep24 import loss as eloss, train as etrain
+    from ep24.options import PlanOptions, set_options
+    torch.manual_seed(0)
+    m = tiny_model()
+    m.head.initialize_biases(1e-2)
+    set_options(m, PlanOptions.parse(plan))
+    B, S = 2, 128                                                          # head levels of 16 x 16, 8 x 8 and 4 x 4 cells
+    ts = etrain.TrainStep(m, eloss.Loss_Function(80), lr=0.0, momentum=0.9, batch=B, size=S, use_graph=True, graph_backward=False)
+    ts.eng.images.copy_(synth.make_images(B, S, seed=1).to(DEV))
+    ts.labels.copy_(synth.make_labels(B, [4, 2], size=S, seed=2).to(DEV))
+    assert [hw for hw, _, _, _ in ts.eng.head_grads] == [256, 64, 16]
+    state0 = ts.state.clone()                                              # the loss's running weights: the same in both steps
+    ts.step()
+    torch.cuda.synchronize()
+    g0 = ts.home.gflat.clone()
+    assert bool(torch.isfinite(g0).all()) and float(g0.abs().max()) > 0
+    ts.eng.backward(torch.full((B, ts.eng.A, ts.eng.ncols), 1e-3, device=DEV))
+    torch.cuda.synchronize()
+    assert not torch.equal(ts.home.gflat, g0)                              # the eager pass really ran, on another gradient
+    ts.state.copy_(state0)
+    ts.step()
+    torch.cuda.synchronize()
+    assert torch.equal(ts.home.gflat, g0)
 
 
 def test_fused_bn_reduce_plan_matches_the_default_plan():
