@@ -21,6 +21,14 @@ __device__ __forceinline__ void store8(bf16* p, const float (&v)[8]) {
     *reinterpret_cast<bf16x8*>(p) = t;
 }
 
+// A row index the optimiser cannot see through (no instruction).  The backward reduce computes its first row and the first batch's
+// row offsets inside the loop over channel-group passes (one pass unless C > 8 * threads); hoisted out of it, the row and the eight
+// 64-bit products stay live across the whole kernel - the 18 registers between four waves per SIMD and spills.
+__device__ __forceinline__ long pinned_row(long m) {
+    asm volatile("" : "+v"(m));
+    return m;
+}
+
 struct RowMap {        // thread -> (row slot, 8-channel group); rows strided by rows_per_pass
     int tpr, rpb;      // threads per row, rows per block
     __device__ RowMap(int C, int nt = 256) { tpr = C >> 3; rpb = tpr >= nt ? 1 : nt / tpr; }
@@ -29,8 +37,20 @@ struct RowMap {        // thread -> (row slot, 8-channel group); rows strided by
 // ---------------------------------------------------------------------------------------- BN + act forward
 // Prologue: the block folds the fixed-point statistics into per-channel scale / shift in LDS (one channel per
 // thread, 2*reps loads).  Body: flat grid-stride over 16-byte chunks, consecutive lanes on consecutive
-// addresses whatever C is, 2 chunks in flight per lane.
-template <int ACT, bool RES>
+// addresses whatever C is, U chunks in flight per lane.
+//
+// FIXED (chosen by the launcher, which knows the grid): the grid stride is a multiple of the channel-group count, so every chunk of
+// a thread belongs to ONE group and its 16 constants live in registers.  As a run-time `fixed_group ? rsc[j] : sc[...]` the select
+// compiled to an s_and_b64 / v_mov_b32 / s_cbranch_vccnz triple per constant - two taken branches per output element, like the
+// `res ? r : 0` below - and the loop carried four copies of the other path's 64-bit division.  !FIXED keeps the constants in LDS and
+// advances (row, group) by the stride's quotient and remainder: no division per chunk either.
+//
+// The U chunks are a ring of one-chunk buffers: a chunk is computed and stored, and its registers are at once refilled with the chunk
+// U places on, so U - 1 loads are in flight under every chunk's arithmetic with the registers of one batch (a second batch of
+// registers would cost the fifth wave per SIMD).  Loads are unconditional (a chunk past the end re-reads the thread's first chunk and
+// is never used) and in straight-line code with the arithmetic, so the compiler waits in descending vmcnt instead of vmcnt(0) at a
+// control-flow join.  Addresses are advanced, not recomputed from a 64-bit product per chunk.
+template <int ACT, bool RES, bool FIXED>
 __global__ __launch_bounds__(256) void bn_act_fwd_kernel(const bf16* z, long ld_z, const long long* stats, int reps,
                                                          const float* gamma, const float* beta, float* rmean,
                                                          float* rvar, long* nbt, long* nbt2, float* save, bf16* y, long ld_y,
@@ -90,55 +110,88 @@ __global__ __launch_bounds__(256) void bn_act_fwd_kernel(const bf16* z, long ld_
         if (nbt2) *nbt2 += 1;                      // a merged unit: the second module's num_batches_tracked
     }
     __syncthreads();
-    const int cgs = C >> 3;
+    const unsigned cgs = (unsigned)C >> 3;
     const long total = M * cgs;
-    const long stride = (long)gridDim.x * 256;
+    const unsigned nthr = gridDim.x * 256u;                       // the grid stride in chunks (at most MAX_BLOCKS * 256)
+    const unsigned t0 = blockIdx.x * 256u + threadIdx.x;          // the thread's first chunk
+    if ((long)t0 >= total) return;
     constexpr int U = 4;
-    // When the grid stride is a multiple of the channel-group count every chunk of a thread belongs to ONE group, so
-    // its 16 constants live in registers.  (Reading them from LDS per chunk - 16 ds_read_b32 with a 32-byte lane
-    // stride, 4-way bank conflicts - made this kernel LDS-bound at ~4.9 TB/s of input: SQ_LDS_BANK_CONFLICT was 81 %
-    // of the LDS-active cycles.)
-    const bool fixed_group = stride % cgs == 0;
-    const int g_fixed = (int)(((long)blockIdx.x * 256 + threadIdx.x) % cgs);
+    // chunk n of the thread is t0 + n * nthr = (row, group); a step adds (qs, rs) and carries a row when the group passes cgs
+    // (FIXED: rs == 0, the group never moves).  Once per thread, 32 bit.
+    const unsigned qs = nthr / cgs, rs = FIXED ? 0u : nthr - qs * cgs;
+    const unsigned row0 = t0 / cgs, g0 = t0 - row0 * cgs;
+    // (Reading the constants from LDS per chunk - 16 ds_read_b32 with a 32-byte lane stride, 4-way bank conflicts - made the FIXED
+    // shapes LDS-bound at ~4.9 TB/s of input: SQ_LDS_BANK_CONFLICT was 81 % of the LDS-active cycles.)
     float rsc[8], rsh[8];
+    if constexpr (FIXED) {
 #pragma unroll
-    for (int j = 0; j < 8; ++j) { rsc[j] = sc[g_fixed * 9 + j]; rsh[j] = sh[g_fixed * 9 + j]; }
-    const long m_fixed = ((long)blockIdx.x * 256 + threadIdx.x) / cgs, m_step = stride / cgs;
-    int it = 0;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += U * stride, ++it) {
-        long mm[U];
-        int gg[U];
-        bf16x8 v[U], r[U];
+        for (int j = 0; j < 8; ++j) { rsc[j] = sc[g0 * 9 + j]; rsh[j] = sh[g0 * 9 + j]; }
+    }
+    struct Cursor {                                // one chunk of the thread: its flat index, group and element offset in an operand
+        long i, off;
+        unsigned g;
+    };
+    // a cursor moves one chunk on: `step` elements, plus `carry` where the group wraps into the next row
+    auto advance = [&](Cursor& c, long step, long carry) {
+        c.i += nthr;
+        c.off += step;
+        if constexpr (!FIXED) {
+            c.g += rs;
+            const bool wrap = c.g >= cgs;
+            c.g -= wrap ? cgs : 0u;
+            c.off += wrap ? carry : 0l;
+        }
+    };
+    const long step_z = (long)qs * ld_z + rs * 8, carry_z = ld_z - C;
+    const long step_y = (long)qs * ld_y + rs * 8, carry_y = ld_y - C;
+    const long step_r = RES ? (long)qs * ld_res + rs * 8 : 0, carry_r = RES ? ld_res - C : 0;
+    const long first_z = (long)row0 * ld_z + g0 * 8, first_r = RES ? (long)row0 * ld_res + g0 * 8 : 0;
+    Cursor lz{(long)t0, first_z, g0}, lr{(long)t0, first_r, g0};             // the next chunk to request (z, residual)
+    Cursor st{(long)t0, (long)row0 * ld_y + g0 * 8, g0};                    // the next chunk to compute and store
+    bf16x8 v[U], r[U];
+    auto request = [&](int k) {
+        const bool ok = lz.i < total;
+        v[k] = *reinterpret_cast<const bf16x8*>(z + (ok ? lz.off : first_z));
+        advance(lz, step_z, carry_z);
+        if constexpr (RES) {
+            r[k] = *reinterpret_cast<const bf16x8*>(res + (ok ? lr.off : first_r));
+            advance(lr, step_r, carry_r);
+        }
+    };
+    auto finish = [&](int k) {
+        bf16x8 o;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const float a_ = FIXED ? rsc[j] : sc[st.g * 9 + j];
+            const float b_ = FIXED ? rsh[j] : sh[st.g * 9 + j];
+            const float u = fmaf((float)v[k][j], a_, b_);
+            if constexpr (RES) o[j] = (bf16)(act_fwd(u, act) + (float)r[k][j]);
+            else o[j] = (bf16)act_fwd(u, act);
+        }
+        *reinterpret_cast<bf16x8*>(y + st.off) = o;
+        advance(st, step_y, carry_y);
+    };
+    // The scheduling barriers keep the requests in chunk order and the loop one chunk at a time.  Left alone the scheduler put the first
+    // chunk's request last (the loop then opens with vmcnt(0)) and ran the chunks' arithmetic side by side behind one wait for three
+    // of the four, with the refills at the end of the iteration.
+#pragma unroll
+    for (int k = 0; k < U; ++k) {
+        request(k);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    while (st.i + (long)U * nthr < total) {                       // a full batch with another one behind it
 #pragma unroll
         for (int k = 0; k < U; ++k) {
-            const long ik = i + k * stride;
-            const bool ok = ik < total;
-            if (fixed_group) {                                   // row = (ik - g) / cgs without a 64-bit division
-                mm[k] = ok ? m_fixed + (long)(it * U + k) * m_step : -1;
-                gg[k] = g_fixed;
-            } else {
-                mm[k] = ok ? ik / cgs : -1;
-                gg[k] = ok ? (int)(ik - mm[k] * cgs) : 0;
-            }
-            if (ok) {
-                v[k] = *reinterpret_cast<const bf16x8*>(z + mm[k] * ld_z + gg[k] * 8);
-                if constexpr (RES) r[k] = *reinterpret_cast<const bf16x8*>(res + mm[k] * ld_res + gg[k] * 8);
-            }
+            finish(k);
+            __builtin_amdgcn_sched_barrier(0);                    // the refill behind the chunk's last use of its registers
+            request(k);
+            __builtin_amdgcn_sched_barrier(0);
         }
+    }
 #pragma unroll
-        for (int k = 0; k < U; ++k) {
-            if (mm[k] < 0) break;
-            bf16x8 o;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const float a_ = fixed_group ? rsc[j] : sc[gg[k] * 9 + j];
-                const float b_ = fixed_group ? rsh[j] : sh[gg[k] * 9 + j];
-                const float u = fmaf((float)v[k][j], a_, b_);
-                if constexpr (RES) o[j] = (bf16)(act_fwd(u, act) + (float)r[k][j]);
-                else o[j] = (bf16)act_fwd(u, act);
-            }
-            *reinterpret_cast<bf16x8*>(y + mm[k] * ld_y + gg[k] * 8) = o;
-        }
+    for (int k = 0; k < U; ++k) {                                 // the last batch
+        if (st.i >= total) break;
+        finish(k);
     }
 }
 
@@ -149,6 +202,10 @@ __global__ __launch_bounds__(256) void bn_act_fwd_kernel(const bf16* z, long ld_
 //   dz = k1*du - k2 - k3*z         (k1 = gamma*invstd, k3 = k1*invstd*mean(du*zhat), k2 = k1*(mean(du) - mean*invstd*mean(du*zhat)))
 // Every thread owns one 8-channel group for the whole kernel (constants in registers) and walks rows with
 // several 16-byte loads in flight.
+
+// Four waves per SIMD (at most 128 registers) for the backward kernels: what they had before the row ring, which without this
+// attribute the register allocator gives up for a handful of registers (130 - 140).  No scratch: tools/isa_summary.py.
+#define EP24_BN_WAVES __attribute__((amdgpu_waves_per_eu(4)))
 
 template <int UNROLL, int NT, int ACT>
 __device__ __forceinline__ void bn_bwd_reduce_body(const bf16* dy, long ld_dy, const bf16* z, long ld_z,
@@ -172,7 +229,7 @@ __device__ __forceinline__ void bn_bwd_reduce_body(const bf16* dy, long ld_dy, c
         float sg[8] = {0, 0, 0, 0, 0, 0, 0, 0}, sb[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         if (active) {
             const long step = (long)nblk * rm.rpb;
-            const long m_first = (long)bid * rm.rpb + slot;
+            const long m_first = pinned_row((long)bid * rm.rpb + slot);
             bf16x8 vdy[UNROLL], vz[UNROLL];
 #pragma unroll
             for (int k = 0; k < UNROLL; ++k) {                  // first batch issued before the constants are needed
@@ -181,6 +238,7 @@ __device__ __forceinline__ void bn_bwd_reduce_body(const bf16* dy, long ld_dy, c
                 const long mm = m_first + k * step < M ? m_first + k * step : (m_first < M ? m_first : 0);
                 vdy[k] = *reinterpret_cast<const bf16x8*>(dy + mm * ld_dy + cg * 8);
                 vz[k] = *reinterpret_cast<const bf16x8*>(z + mm * ld_z + cg * 8);
+                __builtin_amdgcn_sched_barrier(0);               // in row order: the loop below waits for row 0 first
             }
             // ... and they STAY in front of the constants: left to itself the scheduler requested the eight constant vectors first, waited
             // for all of them (their scale / shift arithmetic), and only then issued these eight loads - a second serial round trip in
@@ -193,27 +251,42 @@ __device__ __forceinline__ void bn_bwd_reduce_body(const bf16* dy, long ld_dy, c
                 const float mean = save[c], inv = save[C + c];
                 sc[j] = gamma[c] * inv; sh[j] = beta[c] - mean * sc[j]; iv[j] = inv; mi[j] = mean * inv;
             }
-            for (long m = m_first; m < M; m += UNROLL * step) {
+            auto add_row = [&](int k) {                          // a thread adds its rows in ascending batch, k, j
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    // four elements side by side, then the other four: all eight at once want more temporaries than the 128 registers
+                    // of four waves per SIMD leave beside the 80 of constants, sums and row buffers (spills, and a vmcnt(0) per reload)
+                    if (j == 4) __builtin_amdgcn_sched_barrier(0);
+                    const float zz = (float)vz[k][j];
+                    const float du = (float)vdy[k][j] * act_grad(fmaf(zz, sc[j], sh[j]), act);
+                    sb[j] += du;
+                    sg[j] = fmaf(du, fmaf(zz, iv[j], -mi[j]), sg[j]);
+                }
+            };
+            // The batch's registers are a ring of one-row buffers: a row is added and its registers are at once refilled with the row
+            // UNROLL places on, so UNROLL - 1 row pairs are in flight under every row's arithmetic.  (Refilled as a whole batch AFTER
+            // the batch's arithmetic - what this loop did before - load and arithmetic took turns: HBM idle while the SIMDs computed.)
+            // The refill is unconditional and in straight-line code with the arithmetic (a row past M re-reads the next batch's first
+            // row), so the waits stay descending vmcnt(n).  No second register buffer: at 127 registers it would cost the fourth wave.
+            long m = m_first;
+            for (; m + UNROLL * step < M; m += UNROLL * step) {   // a full batch with another one behind it
 #pragma unroll
                 for (int k = 0; k < UNROLL; ++k) {
-                    if (m + k * step >= M) break;
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        const float zz = (float)vz[k][j];
-                        const float du = (float)vdy[k][j] * act_grad(fmaf(zz, sc[j], sh[j]), act);
-                        sb[j] += du;
-                        sg[j] = fmaf(du, fmaf(zz, iv[j], -mi[j]), sg[j]);
-                    }
+                    add_row(k);
+                    __builtin_amdgcn_sched_barrier(0);           // the refill behind the row's last use of its registers
+                    const long mn = m + (UNROLL + k) * step;
+                    const long mm = mn < M ? mn : m + UNROLL * step;
+                    vdy[k] = *reinterpret_cast<const bf16x8*>(dy + mm * ld_dy + cg * 8);
+                    vz[k] = *reinterpret_cast<const bf16x8*>(z + mm * ld_z + cg * 8);
+                    // one row at a time: the scheduler otherwise hoists the refills over the next rows' arithmetic into registers of
+                    // their own (132 - 172 of them: three waves per SIMD, or two)
+                    __builtin_amdgcn_sched_barrier(0);
                 }
-                if (m + UNROLL * step < M) {                      // another batch follows (uniform per thread): all of it is issued
+            }
 #pragma unroll
-                    for (int k = 0; k < UNROLL; ++k) {
-                        const long mn = m + (UNROLL + k) * step;
-                        const long mm = mn < M ? mn : m;
-                        vdy[k] = *reinterpret_cast<const bf16x8*>(dy + mm * ld_dy + cg * 8);
-                        vz[k] = *reinterpret_cast<const bf16x8*>(z + mm * ld_z + cg * 8);
-                    }
-                }
+            for (int k = 0; k < UNROLL; ++k) {                    // the last batch
+                if (m + k * step >= M) break;
+                add_row(k);
             }
         }
         const int ngrp = min(min(rm.tpr, NT), (C >> 3) - cg0);            // (<= NT: with C > 8 NT a pass covers NT groups, not tpr)
@@ -238,7 +311,7 @@ __device__ __forceinline__ void bn_bwd_reduce_body(const bf16* dy, long ld_dy, c
 }
 
 template <int UNROLL, int NT, int ACT>
-__global__ __launch_bounds__(NT) void bn_act_bwd_reduce_kernel(const bf16* dy, long ld_dy, const bf16* z, long ld_z,
+__global__ __launch_bounds__(NT) EP24_BN_WAVES void bn_act_bwd_reduce_kernel(const bf16* dy, long ld_dy, const bf16* z, long ld_z,
                                                                const float* save, const float* gamma,
                                                                const float* beta, long long* dgamma, long long* dbeta,
                                                                long M, int C, int reps) {
@@ -325,40 +398,69 @@ __device__ __forceinline__ void bn_bwd_apply_body(const bf16* dy, long ld_dy, co
             pgg[0] = a0; pgg[1] = a1; pbg[0] = c0; pbg[1] = c1;
         }
         const long step = (long)nblk * rm.rpb;
-        for (long m = (long)bid * rm.rpb + slot; m < M; m += UNROLL * step) {
-            bf16x8 vdy[UNROLL], vz[UNROLL];
+        long m = (long)bid * rm.rpb + slot;
+        if (m >= M) continue;
+        bf16x8 vdy[UNROLL], vz[UNROLL];
+#pragma unroll
+        for (int k = 0; k < UNROLL; ++k) {
+            // every load is issued (a row past M re-reads the batch's first row and is never used): inside `if (mm < M)` blocks the
+            // control-flow joins made the compiler wait vmcnt(0) for the whole batch
+            const long mm = m + k * step < M ? m + k * step : m;
+            vdy[k] = __builtin_nontemporal_load(reinterpret_cast<const bf16x8*>(dy + mm * ld_dy + cg * 8));
+            vz[k] = __builtin_nontemporal_load(reinterpret_cast<const bf16x8*>(z + mm * ld_z + cg * 8));
+            // in row order: requested last (the scheduler's choice), row 0 made the loop below open with vmcnt(0) in every iteration
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        auto row = [&](int k, bool refill) {
+            bf16* pdz = dz + (m + k * step) * ld_dz + cg * 8;
+            bf16x8 old;
+            if (ACC) old = *reinterpret_cast<const bf16x8*>(pdz);                       // requested in front of the row's arithmetic
+            bf16x8 o;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const float zz = (float)vz[k][j];
+                const float du = (float)vdy[k][j] * act_grad(fmaf(zz, sc[j], sh[j]), act);
+                o[j] = (bf16)fmaf(-k3[j], zz, fmaf(k1[j], du, -k2[j]));
+            }
+            if (ACC) {                            // pre-activation BN over a shared input (DenseNet): dz collects every consumer
+#pragma unroll
+                for (int j = 0; j < 8; ++j) o[j] = (bf16)((float)old[j] + (float)o[j]);
+            }
+            *reinterpret_cast<bf16x8*>(pdz) = o;
+            if (refill) {
+                // behind the row's store, which no load may pass (dz may be dy or z for all the compiler knows), and so behind the last
+                // use of the row's registers: requested in the middle of the arithmetic (the scheduler's choice) the refill needs
+                // registers of its own, and the copies back at the top of the loop wait for every load in flight
+                const long mn = m + (UNROLL + k) * step;
+                const long mm = mn < M ? mn : m + UNROLL * step;
+                vdy[k] = __builtin_nontemporal_load(reinterpret_cast<const bf16x8*>(dy + mm * ld_dy + cg * 8));
+                vz[k] = __builtin_nontemporal_load(reinterpret_cast<const bf16x8*>(z + mm * ld_z + cg * 8));
+            }
+        };
+        // The batch's registers are a ring of one-row buffers: a row is computed and its registers are at once refilled with the row
+        // UNROLL places on - UNROLL - 1 row pairs are in flight under every row's arithmetic and store.  (Load,
+        // arithmetic and store of a batch used to follow each other: 13.5 us for a 32000 x 256 launch whose 48 MB take 7.6 us.)  The
+        // refill is unconditional and in straight-line code with the arithmetic (a row past M re-reads the next batch's first row), so
+        // the waits are descending vmcnt(n).  No second register buffer: at 127 registers it would cost the fourth wave per SIMD.
+        for (; m + UNROLL * step < M; m += UNROLL * step) {      // a full batch with another one behind it
 #pragma unroll
             for (int k = 0; k < UNROLL; ++k) {
-                const long mm = m + k * step;
-                if (mm < M) {
-                    vdy[k] = __builtin_nontemporal_load(reinterpret_cast<const bf16x8*>(dy + mm * ld_dy + cg * 8));
-                    vz[k] = __builtin_nontemporal_load(reinterpret_cast<const bf16x8*>(z + mm * ld_z + cg * 8));
-                }
+                row(k, true);
+                __builtin_amdgcn_sched_barrier(0);               // one row at a time, as in the reduce: registers
             }
+        }
 #pragma unroll
-            for (int k = 0; k < UNROLL; ++k) {
-                const long mm = m + k * step;
-                if (mm >= M) break;
-                bf16x8 o;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const float zz = (float)vz[k][j];
-                    const float du = (float)vdy[k][j] * act_grad(fmaf(zz, sc[j], sh[j]), act);
-                    o[j] = (bf16)fmaf(-k3[j], zz, fmaf(k1[j], du, -k2[j]));
-                }
-                if (ACC) {                        // pre-activation BN over a shared input (DenseNet): dz collects every consumer
-                    const bf16x8 old = *reinterpret_cast<const bf16x8*>(dz + mm * ld_dz + cg * 8);
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) o[j] = (bf16)((float)old[j] + (float)o[j]);
-                }
-                *reinterpret_cast<bf16x8*>(dz + mm * ld_dz + cg * 8) = o;
-            }
+        for (int k = 0; k < UNROLL; ++k) {                        // the last batch
+            if (m + k * step >= M) break;
+            row(k, false);
         }
     }
 }
 
+// (waves per SIMD: four as EP24_BN_WAVES, but at least three for the accumulating form with an activation, which had three before the
+// row ring - its old-value load holds four registers more per row; it reaches four as well now, without being forced to)
 template <int UNROLL, int ACT, bool ACC = false>
-__global__ __launch_bounds__(256) void bn_act_bwd_apply_kernel(const bf16* dy, long ld_dy, const bf16* z, long ld_z,
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ACC && ACT ? 3 : 4))) void bn_act_bwd_apply_kernel(const bf16* dy, long ld_dy, const bf16* z, long ld_z,
                                                                const float* save, const float* gamma, const float* beta,
                                                                const long long* dgamma, const long long* dbeta, float* ggrad,
                                                                float* bgrad, bf16* dz, long ld_dz, long M, int C, int reps) {
@@ -375,7 +477,7 @@ __global__ __launch_bounds__(256) void bn_act_bwd_apply_kernel(const bf16* dy, l
 __device__ unsigned g_bn_barrier_timeouts;
 
 template <int ACT>
-__global__ __launch_bounds__(256) void bn_act_bwd_fused_kernel(const bf16* dy, long ld_dy, const bf16* z, long ld_z,
+__global__ __launch_bounds__(256) EP24_BN_WAVES void bn_act_bwd_fused_kernel(const bf16* dy, long ld_dy, const bf16* z, long ld_z,
                                                                const float* save, const float* gamma, const float* beta,
                                                                long long* dgamma, long long* dbeta, float* ggrad, float* bgrad,
                                                                bf16* dz, long ld_dz, long M, int C, int reps, unsigned* bar) {
@@ -393,6 +495,12 @@ __global__ __launch_bounds__(256) void bn_act_bwd_fused_kernel(const bf16* dy, l
     }
     __syncthreads();
     bn_bwd_apply_body<4, ACT, false, true>(dy, ld_dy, z, ld_z, save, gamma, beta, dgamma, dbeta, ggrad, bgrad, dz, ld_dz, M, C, reps, bid, nblk);
+}
+
+template <bool FIXED>
+auto fwd_kernel(int act, bool residual) {
+    return residual ? (act == 1 ? bn_act_fwd_kernel<1, true, FIXED> : act == 2 ? bn_act_fwd_kernel<2, true, FIXED> : act == 3 ? bn_act_fwd_kernel<3, true, FIXED> : bn_act_fwd_kernel<0, true, FIXED>)
+                    : (act == 1 ? bn_act_fwd_kernel<1, false, FIXED> : act == 2 ? bn_act_fwd_kernel<2, false, FIXED> : act == 3 ? bn_act_fwd_kernel<3, false, FIXED> : bn_act_fwd_kernel<0, false, FIXED>);
 }
 
 int flat_grid(long M, int C, int per_thread) {       // flat 16-byte chunks, `per_thread` chunks per lane
@@ -1227,9 +1335,12 @@ extern "C" int ep24_bn_act_fwd(const void* z, int64_t ld_z, const int64_t* stats
     // statistics for a 16 MB tensor.  4 = one batch of the body's unrolled loop.
     // (swept again in round 3 with the batched prologue, tools/bn_probe.py: 8 wins where C >= 1024 or the tensor is large and narrow)
     const int fw_per = (C >= 1024 || (C <= 128 && M * C >= (12L << 20))) ? 8 : 4;
-    auto kfn = residual ? (act == 1 ? bn_act_fwd_kernel<1, true> : act == 2 ? bn_act_fwd_kernel<2, true> : act == 3 ? bn_act_fwd_kernel<3, true> : bn_act_fwd_kernel<0, true>)
-                        : (act == 1 ? bn_act_fwd_kernel<1, false> : act == 2 ? bn_act_fwd_kernel<2, false> : act == 3 ? bn_act_fwd_kernel<3, false> : bn_act_fwd_kernel<0, false>);
-    hipLaunchKernelGGL(kfn, dim3(flat_grid(M, C, fw_per)), dim3(256), 2 * (C + C / 8) * sizeof(float), S_, (const bf16*)z, ld_z, (const long long*)stats, reps, gamma,
+    const int grid = flat_grid(M, C, fw_per);
+    // one 8-channel group per thread for the whole launch (constants in registers) when the grid stride is a multiple of the group
+    // count: every layer of the flagship network.  A compile-time matter for the kernel: see the comment above it.
+    const bool fixed = (grid * 256L) % (C >> 3) == 0;
+    auto kfn = fixed ? fwd_kernel<true>(act, residual != nullptr) : fwd_kernel<false>(act, residual != nullptr);
+    hipLaunchKernelGGL(kfn, dim3(grid), dim3(256), 2 * (C + C / 8) * sizeof(float), S_, (const bf16*)z, ld_z, (const long long*)stats, reps, gamma,
                        beta, running_mean, running_var, (long*)num_batches, (long*)num_batches2, save, (bf16*)y, ld_y, (const bf16*)residual,
                        ld_res, M, C, eps, momentum);
     EP24_LAUNCH_CHECK("ep24_bn_act_fwd");
