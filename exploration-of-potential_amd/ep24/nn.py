@@ -490,6 +490,13 @@ class YOLOX(nn.Module):
             self._engines[key] = Engine(self, batch, size, dtype)
         return self._engines[key]
 
+    def release_engine(self, batch, size):
+        """Forgets the bf16 launch plan for [batch, 3, size] inputs (``ep24.multiscale`` evicts plans whose activations no longer
+        fit); the caller has synchronised and holds no captured graph of it.  Returns whether there was one."""
+        if not isinstance(size, int) and size[0] == size[1]:
+            size = int(size[0])
+        return self._engines.pop((batch, size), None) is not None
+
     def forward(self, x, train=False, return_fpn=False):
         """``return_fpn=True`` (eval mode only): ``(outputs, fpn_outs)`` as the reference's yolox/models/yolox.py:49 - the three neck
         outputs (strides 8, 16, 32) as NCHW fp32 copies; ``outputs`` is what the call without the flag returns."""

@@ -103,19 +103,27 @@ class Exp(BaseExp):
             kw["collate_fn"] = raw_collate
         return torch.utils.data.DataLoader(self.dataset, **kw)
 
-    def random_resize(self, data_loader=None, epoch=None):
-        """A multiscale input size, multiple of 32, aspect ratio of input_size (exp/yolox_base.py:93-107); plans are cached per size."""
+    def random_resize(self, data_loader=None, epoch=None, rng=None):
+        """A multiscale input size, multiple of 32, aspect ratio of input_size (exp/yolox_base.py:93-107); plans are cached per size.
+        ``rng``: a ``random.Random`` to draw from (``ep24.multiscale.size_for``); None: the module-level ``random``."""
         import random
         size_factor = self.input_size[1] * 1.0 / self.input_size[0]
         if not hasattr(self, "random_size"):
             self.random_size = (int(self.input_size[0] / 32) - self.multiscale_range, int(self.input_size[0] / 32) + self.multiscale_range)
-        size = random.randint(*self.random_size)
+        size = (rng or random).randint(*self.random_size)
         return (int(32 * size), 32 * int(size * size_factor))
 
-    def preprocess(self, inputs, targets, tsize):
+    def preprocess(self, inputs, targets, tsize, out=None):
+        """``out=(images, labels)``: buffers the resized batch is written into (``MultiScaleStep.inputs(tsize)``).  CUDA fp32 batches
+        are resized by ``ep24.multiscale.resize_batch`` (two HIP launches); CPU tensors keep the reference's ``interpolate``."""
         scale_y = tsize[0] / self.input_size[0]
         scale_x = tsize[1] / self.input_size[1]
         if scale_x != 1 or scale_y != 1:
+            import torch
+            if inputs.is_cuda and inputs.dtype == torch.float32:
+                from ep24.multiscale import resize_batch
+                out_images, out_labels = out if out is not None else (None, None)
+                return resize_batch(inputs.contiguous(), targets.contiguous(), tsize, out_images=out_images, out_labels=out_labels)
             inputs = nn.functional.interpolate(inputs, size=tsize, mode="bilinear", align_corners=False)
             targets[..., 1::2] = targets[..., 1::2] * scale_x
             targets[..., 2::2] = targets[..., 2::2] * scale_y

@@ -17,6 +17,8 @@ exp/yolox_base.py:155-167) per iteration, ``--ema`` keeps a ``ModelEMA`` copy (u
 checkpoint, ``--l1`` turns ``use_l1`` on for head and loss from epoch ``exp.L1_epoch`` on (exp/yolox_base.py:38).
 ``--weight-decay [W]`` is the fourth piece of that recipe: stock YOLOX's three optimizer groups (yolox/exp/yolox_base.py:198-224),
 ``exp.weight_decay`` (or W) on every weight that is not a BatchNorm's, applied by the fused update itself.
+``--multiscale`` is the fifth: every ``--multiscale-interval`` steps a new input size (``exp.random_resize``, core/trainer.py:250-254),
+the batch and its labels resized on the GPU (``exp.preprocess``), one captured step per size (``ep24.multiscale.MultiScaleStep``).
 """
 import argparse
 import os
@@ -73,6 +75,7 @@ class Trainer:
         if args.augment and not args.raw_u8:
             raise SystemExit("train_24p.py: --augment works on the raw uint8 batches behind the prefetcher (drop --no-prefetch / --fp32-batches)")
         check_mixup_args(args)
+        check_multiscale_args(args, exp, self.world)
         if args.fisheye_theta is not None:
             check_fisheye_args(args)
         self.train_loader = exp.get_data_loader(args.batch_size, raw_u8=bool(args.raw_u8), workers=args.loader_workers,
@@ -134,7 +137,16 @@ class Trainer:
                 self.ema_model.ema.load_state_dict(ck["ema_model"])
                 self.ema_model.updates = int(ck.get("ema_updates", 0))
         step_fn = None
-        if not args.no_graph:
+        multiscale = bool(getattr(args, "multiscale", False))
+        tsize = tuple(self.input_size)                    # --multiscale: the size of the step; redrawn every --multiscale-interval steps
+        if multiscale:
+            from ep24.multiscale import MultiScaleStep, size_for
+            step_fn = MultiScaleStep(model, self.loss_func, lr=args.learn_rate, momentum=exp.momentum, batch=args.batch_size,
+                                     base_size=tuple(self.input_size), ema=self.ema_model, weight_decay=self.optimizer.weight_decay,
+                                     max_plans=args.multiscale_plans)
+            if self.current_step >= args.multiscale_interval:     # a resumed run: the size its last draw had chosen
+                tsize = tuple(size_for(exp, args.multiscale_seed, self.current_step // args.multiscale_interval))
+        elif not args.no_graph:
             # the optimizer's decay, not the flag's: --resume has restored the checkpoint's value by now
             step_fn = TrainStep(model, self.loss_func, lr=args.learn_rate, momentum=exp.momentum, batch=args.batch_size,
                                 size=tuple(self.input_size), reducer=reducer, ema=self.ema_model, weight_decay=self.optimizer.weight_decay)
@@ -177,8 +189,15 @@ class Trainer:
                         group["lr"] = lr
                     if step_fn is not None:
                         step_fn.set_lr(lr)
-                images, labels = exp.preprocess(images, labels, self.input_size)
-                if step_fn is not None:
+                if multiscale:
+                    images, labels = exp.preprocess(images, labels, tsize, out=step_fn.inputs(tsize))
+                else:
+                    images, labels = exp.preprocess(images, labels, self.input_size)
+                if multiscale:
+                    res = step_fn.step(images, labels, tsize)
+                    if self.current_step % args.multiscale_interval == 0:     # the reference's (progress_in_iter + 1) % 10 == 0
+                        tsize = tuple(size_for(exp, args.multiscale_seed, self.current_step // args.multiscale_interval))
+                elif step_fn is not None:
                     res = step_fn.step(images, labels)
                 else:
                     self.optimizer.zero_grad()
@@ -239,6 +258,9 @@ class Trainer:
                 if pf1 is not None and pf_mark is not None:      # of loader_and_upload: the loader's own work / the (blocking) upload enqueue
                     rec["host_ms_per_step"]["loader_only"] = round((pf1.t_loader - pf_mark[0]) / max(args.throughput_window, 1) * 1e3, 3)
                     rec["host_ms_per_step"]["upload_enqueue_blocking"] = round((pf1.t_upload - pf_mark[1]) / max(args.throughput_window, 1) * 1e3, 3)
+                if multiscale:
+                    rec["multiscale"] = {"sizes": [list(s) for s in step_fn.sizes_seen], "captures": step_fn.captures,
+                                         "resident": len(step_fn.resident)}
                 with open(args.throughput_json, "w") as fh:
                     json.dump(rec, fh)
                 print("throughput %s" % json.dumps(rec))
@@ -390,6 +412,23 @@ def check_mixup_args(args):
         raise SystemExit("train_24p.py: --mixup blends a second image into the mosaic of --augment (add --augment)")
 
 
+def check_multiscale_args(args, exp, world):
+    """--multiscale keeps one captured step per input size: it needs the captured step, a single process and a range of sizes."""
+    if not getattr(args, "multiscale", False):
+        return
+    if args.no_graph:
+        raise SystemExit("train_24p.py: --multiscale keeps one captured step per input size (ep24.multiscale.MultiScaleStep); drop --no-graph")
+    if world > 1:
+        raise SystemExit("train_24p.py: --multiscale under WORLD_SIZE=%d: the gradient reducer plans its buckets for one engine; "
+                         "multiscale training across ranks is out of scope (run a single process)" % world)
+    if args.multiscale_interval < 1:
+        raise SystemExit("train_24p.py: --multiscale-interval %d: a new size is drawn every N >= 1 steps" % args.multiscale_interval)
+    if args.multiscale_plans < 0:
+        raise SystemExit("train_24p.py: --multiscale-plans %d is negative (0 = as many plans as the device memory holds)" % args.multiscale_plans)
+    if not getattr(exp, "multiscale_range", 0) and not hasattr(exp, "random_size"):
+        raise SystemExit("train_24p.py: --multiscale with exp.multiscale_range == 0 and no exp.random_size: there is one size only")
+
+
 def check_fisheye_args(args):
     """--fisheye-theta works on the raw uint8 batches, and the warp is not composed with mosaic / affine."""
     lo, hi = args.fisheye_theta
@@ -449,6 +488,13 @@ def make_parser():
     p.add_argument("--mixup", action="store_true", help="with --augment: mixup on the GPU (a second image of the batch, letterboxed, "
                    "jittered, mirrored and cropped, averaged into every mosaic image; its 24-point labels re-cast and appended) with the "
                    "Exp's mixup_prob / mixup_scale, iff exp.enable_mixup")
+    p.add_argument("--multiscale", action="store_true", help="stock YOLOX's multiscale training: a new input size from exp.random_resize "
+                   "(multiples of 32 within exp.multiscale_range of input_size / 32) every --multiscale-interval steps, the batch and "
+                   "its labels resized on the GPU behind loader and augmentation, one captured step per size; single process, captured step only")
+    p.add_argument("--multiscale-interval", default=10, type=int, metavar="N", help="steps between two draws of the input size")
+    p.add_argument("--multiscale-seed", default=0, type=int, metavar="S", help="the k-th size follows from (S, k): a resumed run continues the sequence")
+    p.add_argument("--multiscale-plans", default=0, type=int, metavar="N", help="captured steps kept resident, least recently used evicted "
+                   "(0: as many as the free device memory holds)")
     p.add_argument("--augment-seed", default=0, type=int, help="seed of the augmentation; a batch's parameters follow from (seed, epoch, iteration)")
     p.add_argument("--fisheye-theta", default=None, type=int, nargs=2, metavar=("LO", "HI"), help="fisheye sector warp of every image AND its "
                    "24-point labels on the GPU (ep24.fisheye.FisheyeTransform behind the prefetcher), one angle in [LO, HI] degrees per image, "

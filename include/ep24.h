@@ -796,6 +796,16 @@ int ep24_preproc_u8(const uint8_t* images, const int64_t* desc, const double* sc
  * y columns (v*height)*r, first max_labels rows, zero padded. */
 int ep24_preproc_labels(const double* rows, const int64_t* row_off, const double* whr, int n, float* out, int max_labels,
                         void* stream);
+/* Multiscale training (Exp.preprocess, exp/yolox_base.py:109-118).  Bilinear resize of n contiguous fp32 planes sh x sw -> dh x dw
+ * (n = B*3 for a batch; any positive sizes) with the result of F.interpolate(mode="bilinear", align_corners=False), the source
+ * coordinates in DOUBLE: per axis s = (double)n_in / n_out, src = max(s*(d + 0.5) - 0.5, 0), i0 = min((int)src, n_in-1),
+ * i1 = min(i0 + 1, n_in-1), w1 = (float)(src - i0), w0 = 1.0f - w1; then in fp32, every operation rounded on its own,
+ * top = a*wx0 + b*wx1, bot = c*wx0 + d*wx1, out = top*wy0 + bot*wy1 (a, b from row y0; c, d from row y1).  Equal sizes: a copy.
+ * A plane (source and destination) holds at most 2^31 - 1 elements. */
+int ep24_resize_bilinear_f32(const float* src, int n, int sh, int sw, float* dst, int dh, int dw, void* stream);
+/* The label half: rows x 51 floats; column 0 (the class) copied, odd columns * scale_x, even columns >= 2 * scale_y (one rounded fp32
+ * multiply each: targets[..., 1::2] * scale_x, targets[..., 2::2] * scale_y).  out == in is allowed.  rows <= 2^40. */
+int ep24_scale_labels(const float* in, float* out, int64_t rows, float scale_x, float scale_y, void* stream);
 
 /* Training augmentation (mosaic, random affine, mixup, mirror, HSV), two launches per batch.  Every output image
  * is assembled from up to four TILES: a tile is one source image, resized by s = min(S_h/h, S_w/w) as preproc resizes it and
