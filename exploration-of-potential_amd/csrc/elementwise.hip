@@ -931,15 +931,17 @@ __global__ __launch_bounds__(256) void rows_copy_kernel(const bf16* src, long ld
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
         const int cg = (int)(i % cgs);
         const long m = i / cgs;
-        float v[8];
-        load8(src + m * ld_src + cg * 8, v);
         bf16* d = dst + m * ld_dst + cg * 8;
-        if (accumulate) {
-            float o[8];
-            load8(d, o);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) v[j] += o[j];
+        if (!accumulate) {
+            // a copy moves the 16 bytes as they are: through fp32 and back NaN payloads did not survive
+            *reinterpret_cast<bf16x8*>(d) = *reinterpret_cast<const bf16x8*>(src + m * ld_src + cg * 8);
+            continue;
         }
+        float v[8], o[8];
+        load8(src + m * ld_src + cg * 8, v);
+        load8(d, o);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] += o[j];
         store8(d, v);
     }
 }
@@ -1430,6 +1432,7 @@ extern "C" int ep24_bn_act_bwd_apply_acc(const void* dy, int64_t ld_dy, const vo
 
 extern "C" int ep24_stem_pack(const float* images, void* rows, int64_t ld, int B, int H, int W, void* stream) {
     EP24_REQUIRE(images && rows && H % 2 == 0 && W % 2 == 0 && B > 0 && ld >= 108 && ld % 8 == 0, EP24_E_ARG, "stem_pack: bad arguments");
+    EP24_REQUIRE(((uintptr_t)images & 7) == 0, EP24_E_ARG, "stem_pack: images must be 8-byte aligned (the kernel loads pixel pairs)");
     long sp_blocks = ((long)B * (H / 2) * (W / 2) + 31) / 32;
     hipLaunchKernelGGL(stem_pack_kernel, dim3((unsigned)(sp_blocks > 16384 ? 16384 : sp_blocks)), dim3(256), 0, S_, images,
                        (bf16*)rows, B, H, W, (int)ld);
@@ -1451,6 +1454,8 @@ extern "C" int ep24_spp_fwd(const void* x, int64_t ld_x, void* y5, void* y9, voi
     EP24_REQUIRE(x && y5 && y9 && y13 && idx && C % 8 == 0 && ld_x % 8 == 0 && ld_y % 8 == 0, EP24_E_ARG, "spp_fwd: bad arguments");
     if (scratch) {
         const long n = (long)B * H * W * C;
+        // the column pass reads the row pass's offsets, stored behind 6 * n bytes of row maxima, 8 bytes at a time
+        EP24_REQUIRE(((uintptr_t)scratch & 7) == 0, EP24_E_ARG, "spp_fwd: scratch must be 8-byte aligned");
         bf16* h = (bf16*)scratch;
         uint8_t* hx = (uint8_t*)scratch + 6 * n;
         hipLaunchKernelGGL(spp_row_kernel, dim3(cap_grid(n / 8)), dim3(256), 0, S_, (const bf16*)x, ld_x, h, hx, B, H, W, C);
@@ -1468,6 +1473,7 @@ extern "C" int ep24_spp_fwd(const void* x, int64_t ld_x, void* y5, void* y9, voi
 extern "C" int ep24_spp_bwd(const void* dy5, const void* dy9, const void* dy13, int64_t ld_dy, const uint8_t* idx, void* dx,
                             int64_t ld_dx, int accumulate, int B, int H, int W, int C, void* stream) {
     EP24_REQUIRE(dy5 && dy9 && dy13 && idx && dx && C % 8 == 0 && ld_dy % 8 == 0 && ld_dx % 8 == 0, EP24_E_ARG, "spp_bwd: bad arguments");
+    EP24_REQUIRE(((uintptr_t)idx & 7) == 0, EP24_E_ARG, "spp_bwd: idx must be 8-byte aligned (8 winner codes per load)");
     const size_t lds = (size_t)H * W * 112;                     // the whole map of one (image, channel group) in LDS
     if (lds <= 64 * 1024 && H * W <= 1024)
         hipLaunchKernelGGL(spp_bwd_lds_kernel, dim3(C / 8, B), dim3(256), lds, S_, (const bf16*)dy5, (const bf16*)dy9, (const bf16*)dy13,

@@ -305,7 +305,8 @@ int ep24_f32_colsum(const float* g, int64_t ld, float* db, int64_t M, int N, voi
  * a1/a2  glue ops of the graph
  * ------------------------------------------------------------------------------------------------ */
 /* Focus + im2col for the 3x3 stem: images [B,3,S,S] fp32 NCHW -> rows [B*(S/2)^2][ld] bf16, columns
- * (kh,kw,c4) with c4 = TL,BL,TR,BR x 3 channels, 108 real + zero padding to ld (network_blocks.py:188-210). */
+ * (kh,kw,c4) with c4 = TL,BL,TR,BR x 3 channels, 108 real + zero padding to ld (network_blocks.py:188-210).  images must be
+ * 8-byte aligned (pixel pairs are one load), as for ep24_focus_pack. */
 int ep24_stem_pack(const float* images, void* rows, int64_t ld, int B, int H, int W, void* stream);
 
 /* The Focus stem without an im2col buffer (round 3; network_blocks.py:188-210, Focus.forward + its BaseConv 3x3 over 12 channels).
@@ -327,10 +328,10 @@ int ep24_stem_conv_wgrad_splits(int B, int FH, int FW, int Cout);
 /* SPP max pools k = 5, 9, 13, stride 1, pad k/2 over x[B,H,W,C] (network_blocks.py:131-143).  Writes the
  * three pooled maps into y5/y9/y13 (row stride ld_y) and the winning window offset (dy*16+dx biased by 8)
  * into idx [3][B*H*W][C] uint8 for the backward (first maximum in row-major window order, as ATen).
- * scratch: 9*B*H*W*C bytes for the separable two-pass form (row maxima + their column offsets); null = one pass. */
+ * scratch: 9*B*H*W*C bytes, 8-byte aligned, for the separable two-pass form (row maxima + their column offsets); null = one pass. */
 int ep24_spp_fwd(const void* x, int64_t ld_x, void* y5, void* y9, void* y13, int64_t ld_y, uint8_t* idx,
                  int B, int H, int W, int C, void* scratch, void* stream);
-/* dx (+)= routed gradients of the three pools. */
+/* dx (+)= routed gradients of the three pools.  idx must be 8-byte aligned (the codes of 8 channels are one load). */
 int ep24_spp_bwd(const void* dy5, const void* dy9, const void* dy13, int64_t ld_dy, const uint8_t* idx,
                  void* dx, int64_t ld_dx, int accumulate, int B, int H, int W, int C, void* stream);
 
@@ -347,7 +348,7 @@ int ep24_memset_zero(void* p, int64_t bytes, void* stream);
 int ep24_cast_f32_bf16(const float* src, void* dst, int64_t n, void* stream);
 int ep24_cast_bf16_f32(const void* src, float* dst, int64_t n, void* stream);
 
-/* strided row copy / add:  dst[m, 0:C] (=|+=) src[m, 0:C]  (bf16). */
+/* strided row copy / add:  dst[m, 0:C] (=|+=) src[m, 0:C]  (bf16).  The copy moves every bit pattern unchanged (NaN payloads, -0). */
 int ep24_rows_copy(const void* src, int64_t ld_src, void* dst, int64_t ld_dst, int accumulate, int64_t M, int C,
                    void* stream);
 
