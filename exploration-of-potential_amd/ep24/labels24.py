@@ -5,8 +5,8 @@
 launch (one workgroup per object and ray), ``hull_areas`` the convex-hull area of the acceptance filter
 (``cv2.contourArea(cv2.convexHull(pts))``, :175-176), ``label_rows`` the two txt rows of an accepted annotation
 (:181-193) and ``save_rows`` / ``load_rows`` the on-disk format (``%d`` + 50 or 26 times ``%0.4f``, :214-236; read back
-by ``np.loadtxt`` in datasets/coco24p.py:46).  Decoding COCO polygons / RLE into masks (pycocotools ``annToMask``) stays
-on the host and is not part of this module.
+by ``np.loadtxt`` in datasets/coco24p.py:46).  Decoding COCO polygons / RLE into masks (pycocotools ``annToMask``) is
+ep24.cocomask: its ``decode_batch`` returns the device buffer and descriptor table ``rays_from_buffer`` takes.
 """
 import numpy as np
 import torch
@@ -32,10 +32,8 @@ def rays_batch(masks, centres, device="cuda:0"):
     _lib.require_gpu()
     n = len(masks)
     dev = torch.device(device)
-    pts = torch.empty(n, 24, 2, dtype=torch.int32, device=dev)
-    rad = torch.empty(n, 24, dtype=torch.float64, device=dev)
     if n == 0:
-        return pts, rad
+        return torch.empty(0, 24, 2, dtype=torch.int32, device=dev), torch.empty(0, 24, dtype=torch.float64, device=dev)
     desc, flat, off = [], [], 0
     for m in masks:
         m = m if isinstance(m, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(m))
@@ -50,12 +48,27 @@ def rays_batch(masks, centres, device="cuda:0"):
         flat.append(m.reshape(-1))
         off += H * W
     buf = torch.cat([f.to(dev, non_blocking=True) for f in flat])
-    desc_t = torch.tensor(desc, dtype=torch.int64, device=dev)
+    return rays_from_buffer(buf, torch.tensor(desc, dtype=torch.int64, device=dev), centres)
+
+
+def rays_from_buffer(buf, desc, centres):
+    """buf: uint8 device buffer holding the masks (non-zero = object); desc: int64 [n,6] on the same device, the table of
+    ep24_ray24 ({byte offset, H, W, L, samples, row stride}; ep24.cocomask.decode_batch returns both); centres: [n,2].
+    Returns (points int32 [n,24,2], distances float64 [n,24]) as device tensors."""
+    _lib.require_gpu()
+    n, dev = int(desc.shape[0]), buf.device
+    if buf.dtype != torch.uint8 or desc.dtype != torch.int64 or desc.dim() != 2 or desc.shape[1] != 6 or desc.device != dev:
+        raise ValueError("buf is a uint8 device buffer, desc int64 [n,6] on the same device")
+    pts = torch.empty(n, 24, 2, dtype=torch.int32, device=dev)
+    rad = torch.empty(n, 24, dtype=torch.float64, device=dev)
+    if n == 0:
+        return pts, rad
+    buf, desc = buf.contiguous(), desc.contiguous()
     cen = torch.as_tensor(np.asarray(centres, dtype=np.float64).reshape(n, 2)).to(dev)
     rot = _rot_table(dev)
     for lo in range(0, n, 65535):
         hi = min(n, lo + 65535)
-        call("ray24", ptr(buf), ptr(desc_t, lo * 6), ptr(cen, lo * 2), ptr(rot), hi - lo, ptr(pts, lo * 48), ptr(rad, lo * 24),
+        call("ray24", ptr(buf), ptr(desc, lo * 6), ptr(cen, lo * 2), ptr(rot), hi - lo, ptr(pts, lo * 48), ptr(rad, lo * 24),
              stream_ptr())
     return pts, rad
 

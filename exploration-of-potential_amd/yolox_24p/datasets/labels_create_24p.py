@@ -1,39 +1,49 @@
 """Offline 24-point label generation with the reference's ``Polygon_24`` surface (datasets/2+24_labels_create.py):
 
     cd exploration-of-potential_amd/yolox_24p
-    python datasets/labels_create_24p.py --json instances_train2017.json --images train2017 --out COCO_24p_label
+    python datasets/labels_create_24p.py --json instances_train2017.json --images train2017 --out COCO_24p_label --decoder gpu
 
 ``json_anno_process`` walks the COCO annotations exactly as the reference does (:122-199: crowds, areas below one pixel and
 annotations whose image file is missing are skipped; class ids are re-indexed to 0..79; box centre = bbox corner + half
 size), but the ray casting, the convex-hull area of the acceptance filter and nothing else run on the GPU for a whole
 batch of annotations at a time (ep24.labels24 -> ep24_ray24 / ep24_hull_area24).  ``save_24r_to_txt`` writes the
-reference's files (``%d`` + 50 x ``%0.4f`` in "Cord" mode, + 26 in "Radius" mode).  Mask decoding needs pycocotools,
-which this image does not ship: the class raises ImportError with that message when it is constructed without it.
+reference's files (``%d`` + 50 x ``%0.4f`` in "Cord" mode, + 26 in "Radius" mode).  The masks come from one of two decoders:
+``decoder="pycocotools"`` (the default, the reference's ``coco.annToMask`` on the host; the class raises ImportError with that
+name when it is constructed without the package) or ``decoder="gpu"`` (ep24.cocomask: the same masks decoded into the device
+buffer the rays read, no pycocotools, image sizes from the json's ``images``).
 """
 import argparse
 import json
 import os
+import sys
 from pathlib import Path
 
 import numpy as np
 
-import _path  # noqa: F401
-from ep24 import labels24
+_TOP = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if _TOP not in sys.path:                  # `python datasets/labels_create_24p.py` puts datasets/ first, not yolox_24p/
+    sys.path.insert(0, _TOP)
+import _path  # noqa: F401,E402
+from ep24 import cocomask, labels24  # noqa: E402
 
 # the 80 "thing" category ids of COCO 2017 in ascending order -> contiguous class index (:36-51)
 COCO_IDS = [i for i in range(1, 91) if i not in (12, 26, 29, 30, 45, 66, 68, 69, 71, 83)]
 
 
 class Polygon_24:
-    def __init__(self, mode="Cord", json_label_pth=None, image_data_pth=None, new_label_pth="./COCO_24p_label", batch=1024):
-        try:
-            from pycocotools.coco import COCO
-        except ImportError as e:
-            raise ImportError("labels_create_24p needs pycocotools to decode COCO masks (annToMask)") from e
-        self.mode = mode
+    def __init__(self, mode="Cord", json_label_pth=None, image_data_pth=None, new_label_pth="./COCO_24p_label", batch=1024,
+                 decoder="pycocotools"):
+        if decoder not in ("pycocotools", "gpu"):
+            raise ValueError("decoder is 'pycocotools' or 'gpu'")
+        if decoder == "pycocotools":
+            try:
+                from pycocotools.coco import COCO
+            except ImportError as e:
+                raise ImportError("labels_create_24p needs pycocotools to decode COCO masks (annToMask), or decoder='gpu'") from e
+        self.mode, self.decoder = mode, decoder
         self.json_label_pth, self.image_data_pth, self.new_label_pth = json_label_pth, image_data_pth, new_label_pth
         self.batch = batch
-        self.coco = COCO(self.json_label_pth)
+        self.coco = COCO(self.json_label_pth) if decoder == "pycocotools" else None
         self.json_dict = self.load_label_json()
         self.label_dict_cord24, self.label_dict_radius = {}, {}
         self.coco_id2idx = {str(cid): i for i, cid in enumerate(COCO_IDS)}
@@ -48,11 +58,14 @@ class Polygon_24:
     def _flush(self, pending, area_t_low, area_t_high):
         if not pending:
             return
-        names, cls, centres, masks, areas = zip(*pending)
-        pts, rad = labels24.rays_batch(list(masks), centres)
+        names, cls, centres, masks, areas, shapes = zip(*pending)
+        if self.decoder == "gpu":                             # masks are segmentations: decoded where the rays read them
+            buf, desc = cocomask.decode_batch(list(masks), list(shapes))
+            pts, rad = labels24.rays_from_buffer(buf, desc, centres)
+        else:
+            pts, rad = labels24.rays_batch(list(masks), centres)
         hull = labels24.hull_areas(pts)
-        keep, cord, radius = labels24.label_rows(cls, centres, [m.shape for m in masks], pts, rad, hull, areas, area_t_low,
-                                                 area_t_high)
+        keep, cord, radius = labels24.label_rows(cls, centres, list(shapes), pts, rad, hull, areas, area_t_low, area_t_high)
         for j, i in enumerate(np.nonzero(keep)[0]):
             self.label_dict_cord24[names[i]].append(cord[j])
             self.label_dict_radius[names[i]].append(radius[j])
@@ -69,11 +82,15 @@ class Polygon_24:
                 continue
             if not os.path.exists(Path(self.image_data_pth) / Path(name + ".jpg")):
                 continue
-            mask = self.coco.annToMask(anno)                  # uint8 [H,W]; the json's height / width = the image's
-            assert tuple(mask.shape) == tuple(sizes.get(anno["image_id"], mask.shape))
+            if self.decoder == "gpu":
+                mask, shape = anno["segmentation"], tuple(sizes[anno["image_id"]])
+            else:
+                mask = self.coco.annToMask(anno)              # uint8 [H,W]; the json's height / width = the image's
+                shape = tuple(mask.shape)
+                assert shape == tuple(sizes.get(anno["image_id"], shape))
             cx = anno["bbox"][0] + anno["bbox"][2] / 2
             cy = anno["bbox"][1] + anno["bbox"][3] / 2
-            pending.append((name, self.coco_id2idx[str(anno["category_id"])], (cx, cy), mask, anno["area"]))
+            pending.append((name, self.coco_id2idx[str(anno["category_id"])], (cx, cy), mask, anno["area"], shape))
             if len(pending) >= self.batch:
                 self._flush(pending, area_t_low, area_t_high)
         self._flush(pending, area_t_low, area_t_high)
@@ -93,7 +110,9 @@ if __name__ == "__main__":
     ap.add_argument("--images", required=True)
     ap.add_argument("--out", default="./COCO_24p_label")
     ap.add_argument("--mode", default="Cord", choices=["Cord", "Radius"])
+    ap.add_argument("--decoder", default="pycocotools", choices=["pycocotools", "gpu"],
+                    help="where annToMask runs: pycocotools on the host, or the ep24.cocomask kernels (no pycocotools needed)")
     a = ap.parse_args()
-    polygon = Polygon_24(a.mode, a.json, a.images, a.out)
+    polygon = Polygon_24(a.mode, a.json, a.images, a.out, decoder=a.decoder)
     polygon.json_anno_process()
     polygon.save_24r_to_txt()

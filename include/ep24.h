@@ -783,6 +783,25 @@ int ep24_ray24(const uint8_t* masks, const int64_t* desc, const double* centre, 
 /* cv2.contourArea(cv2.convexHull(points)) of each object's 24 integer points (:175-176): area[n] double. */
 int ep24_hull_area24(const int32_t* pts, int n, double* area, void* stream);
 
+/* COCO segmentations -> the instance masks ep24_ray24 reads (pycocotools annToMask: rleFrPoly, rleMerge as a union, rleDecode),
+ * csrc/cocomask.hip.  masks: one device buffer of `total` bytes, 4-byte aligned, total a multiple of 4, zeroed by the caller before
+ * the first call; desc[n][6] as for ep24_ray24; every mask is uint8 0 / 1, row-major [H, W], at its byte offset.  No kernel writes
+ * outside [0, total) or outside the mask its descriptor names.
+ * ep24_cocomask_poly_xor: one round (at most 7 polygons of every annotation).  edges[ne][8] int32 = {xs, ys, xe, ye, annotation,
+ *   bit 0..6 = the polygon's index within the annotation modulo 7, 1 on the first edge of its polygon, 0}, the vertices being
+ *   (int)(5 * x + .5) / (int)(5 * y + .5) with the polygon closed; the edges of a polygon are adjacent and in its order, and edges[0]
+ *   starts one.  start[ne + 1] int64 = running sum of max(|xe - xs|, |ye - ys|) + 1 (its first entry may be any base), npts =
+ *   start[ne] - start[0].  Every dense point that is a boundary point of rleFrPoly flips its bit of mask byte [y][x].
+ * ep24_cocomask_poly_scan: finishes a round.  items[n] int32 (n <= 65535) = annotation * 2 + (1 if this is the annotation's last
+ *   round); every column's running XOR of bits 0..6, OR bit 7, goes back as 0 / 1 (last round) or into bit 7.  max_w = largest W.
+ * ep24_cocomask_rle: runs[n][3] int64 (n <= 65535) = {annotation, first entry in ends, number of runs}; ends = inclusive prefix
+ *   sums of each annotation's column-major run lengths (the first run is of zeros, runs may be empty); max_w = largest W. */
+int ep24_cocomask_poly_xor(uint8_t* masks, int64_t total, const int64_t* desc, const int32_t* edges, const int64_t* start, int ne,
+                           int64_t npts, void* stream);
+int ep24_cocomask_poly_scan(uint8_t* masks, int64_t total, const int64_t* desc, const int32_t* items, int n, int max_w, void* stream);
+int ep24_cocomask_rle(uint8_t* masks, int64_t total, const int64_t* desc, const int64_t* runs, const int64_t* ends, int n,
+                      int max_w, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * N1  input pipeline (yolox_24p/datasets/data_augment.py:109-174)
  * ------------------------------------------------------------------------------------------------ */
