@@ -9,6 +9,11 @@ The host does O(vertices) numpy work: the integer vertices ``(int)(5 * x + .5)``
 ``max(|dx|, |dy|) + 1`` and their prefix sums.  The dense points, the boundary points among them and the pixels are the
 kernels' (csrc/cocomask.hip).  An annotation's polygons go in rounds of 7 (one mask bit each, bit 7 carries the union of
 the earlier rounds).  Compressed RLE strings are parsed into run lengths here; the runs are decoded on the GPU.
+
+The other direction, masks -> COCO run lengths (pycocotools' ``rleEncode`` and ``rleToString``; csrc/rle.hip): ``encode(packed)``
+for a ``masks.PackedMasks``, ``encode_buffer(buf, desc)`` for the byte buffer ``decode_batch`` returns - together the GPU form of
+``frPyObjects`` + ``merge`` - both giving ``RunLengths`` on the device; ``RunLengths.to_coco()`` copies the runs (not the pixels)
+to the host and writes the compressed strings there with numpy (``rle_string_from_counts``).
 """
 from itertools import chain
 
@@ -16,7 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import call, ptr, stream_ptr
+from ._lib import Ep24Error, call, ptr, stream_ptr
 
 ROUND = 7                                   # polygons of one annotation per xor / scan round
 COORD_LIMIT = float(1 << 20)                # |x|, |y| of a vertex, in pixels
@@ -176,3 +181,151 @@ def ann_to_mask(segmentation, h, w, device="cuda:0"):
     """``COCO.annToMask`` for one annotation's ``segmentation``: uint8 [h, w] of 0 / 1 as a numpy array."""
     buf, _ = decode_batch([segmentation], [(h, w)], device)
     return buf[: h * w].view(h, w).cpu().numpy()
+
+
+def rle_string_from_counts(counts, offsets=None):
+    """rleToString, the inverse of ``rle_counts_from_string``: from the fourth count on the value stored is the difference to
+    the count two before; a value goes out 5 bits at a time, lowest first, as ``chr(48 + bits)`` with 0x20 set while more
+    follow (for a value whose bit 0x10 is set "more" means the rest is not -1, otherwise not 0).  ``counts``: one mask's run
+    lengths -> str.  With ``offsets [n + 1]`` the runs of n masks behind each other (mask i owns ``counts[offsets[i] :
+    offsets[i + 1]]``) -> list of n str.  Numpy over all runs of all masks at once: one pass per character position."""
+    c = np.asarray(counts, dtype=np.int64).reshape(-1)
+    single = offsets is None
+    off = np.array([0, c.size], dtype=np.int64) if single else np.asarray(offsets, dtype=np.int64).reshape(-1)
+    if off.size < 1 or off[0] != 0 or off[-1] != c.size or (np.diff(off) < 0).any():
+        raise ValueError("offsets start at 0, do not decrease and end at len(counts)")
+    n = off.size - 1
+    first = np.repeat(off[:-1], np.diff(off))
+    late = np.flatnonzero(np.arange(c.size) - first > 2)
+    x = c.copy()
+    x[late] -= c[late - 2]
+    chars, lives, alive = [], [], np.ones(c.size, dtype=bool)
+    while alive.any():                                                       # at most 13 rounds for an int64, 7 for an int32
+        ch = x & 0x1f
+        x >>= 5
+        more = np.where(ch & 0x10, x != -1, x != 0) & alive
+        chars.append(ch + 32 * more + 48)
+        lives.append(alive)
+        alive = more
+    if not chars:
+        return "" if single else [""] * n
+    live = np.stack(lives, 1)
+    text = np.stack(chars, 1)[live].astype(np.uint8).tobytes().decode("ascii")     # row-major: run by run, low bits first
+    at = np.concatenate([[0], np.cumsum(live.sum(1))])[off]
+    return text if single else [text[at[i]:at[i + 1]] for i in range(n)]
+
+
+class RunLengths:
+    """COCO run lengths of n masks on the device: ``offsets`` int64 ``[n + 1]``, ``counts`` int32 ``[offsets[n]]`` - mask i owns
+    ``counts[offsets[i] : offsets[i + 1]]``, column-major runs starting with a run of zeros (rleEncode).  ``size``: ``(H, W)``
+    of all masks (``encode``), or a list of ``(h, w)`` per mask (``encode_buffer``); ``sizes`` is always the list."""
+
+    def __init__(self, offsets, counts, size):
+        self.offsets, self.counts, self.size = offsets, counts, size
+
+    def __len__(self):
+        return int(self.offsets.shape[0]) - 1
+
+    @property
+    def sizes(self):
+        if isinstance(self.size, tuple):
+            return [self.size] * len(self)
+        return list(self.size)
+
+    def to_coco(self, compress=True):
+        """-> a list of ``{"size": [h, w], "counts": str}`` (pycocotools' compressed form), or lists of ints with
+        ``compress=False``.  One device-to-host copy each of ``offsets`` and ``counts`` - runs, not pixels; the strings are
+        written on the host by ``rle_string_from_counts``."""
+        off, cnt = self.offsets.cpu().numpy(), self.counts.cpu().numpy()
+        if compress:
+            each = rle_string_from_counts(cnt, off)
+        else:
+            each = [cnt[off[i]:off[i + 1]].tolist() for i in range(len(off) - 1)]
+        return [{"size": [int(h), int(w)], "counts": c} for (h, w), c in zip(self.sizes, each)]
+
+
+def _check_out(out, n):
+    if out is None:
+        return
+    ok = isinstance(out, (tuple, list)) and len(out) == 2 and all(isinstance(t, torch.Tensor) for t in out)
+    if ok:
+        o, c = out
+        ok = (o.dtype == torch.int64 and c.dtype == torch.int32 and o.dim() == c.dim() == 1 and o.is_contiguous()
+              and c.is_contiguous() and o.numel() >= n + 1 and o.device == c.device)
+    if not ok:
+        raise ValueError("out is (offsets, counts): contiguous int64 [>= %d] and int32 tensors on one device" % (n + 1))
+
+
+def _encode_packed(bits, tab, n, H, W, ncols, size, out):
+    """count, scan, the 8-byte read of offsets[n], emit, counts.  tab None: n masks of H x W; else H, W = the largest."""
+    dev, s = bits.device, stream_ptr()
+    colcnt = torch.empty(max(ncols, 1), dtype=torch.int32, device=dev)
+    offsets = torch.empty(n + 1, dtype=torch.int64, device=dev) if out is None else out[0][:n + 1]
+    call("rle_count", ptr(bits), ptr(tab), n, H, W, ptr(colcnt), s)
+    call("rle_scan", ptr(colcnt), ptr(tab), n, H, W, ptr(offsets), s)
+    total = int(offsets[n:].cpu()[0])                                        # the one read that sizes counts
+    if out is None:
+        counts = torch.empty(total, dtype=torch.int32, device=dev)
+    elif out[1].numel() < total:
+        raise Ep24Error("ep24: encode: out's counts hold %d runs, the masks have %d" % (out[1].numel(), total))
+    else:
+        counts = out[1][:total]
+    ends = torch.empty(max(total, 1), dtype=torch.int32, device=dev)
+    call("rle_emit", ptr(bits), ptr(tab), n, H, W, ptr(colcnt), ptr(offsets), ptr(ends), total, s)
+    call("rle_counts", ptr(ends), ptr(offsets), ptr(tab), n, H, W, total, ptr(counts), s)
+    return RunLengths(offsets, counts, size)
+
+
+def encode(packed, out=None):
+    """``masks.PackedMasks`` -> ``RunLengths`` (pycocotools' ``encode`` of the same masks), both tensors on the device.  All
+    compute runs as HIP kernels (csrc/rle.hip): transitions counted per column, an ordered scan, positions emitted, differences
+    taken.  Between the scan and the emit there is one 8-byte device-to-host read of ``offsets[N]`` to size ``counts``; nothing
+    else leaves the device.  ``out = (offsets, counts)``: contiguous int64 ``[>= N + 1]`` and int32 device tensors to write
+    into (their first entries become the result; nothing beyond them is written; too few ``counts`` raise ``Ep24Error``)."""
+    from .masks import PackedMasks, _size
+    if not isinstance(packed, PackedMasks):
+        raise IndexError("encode takes PackedMasks, got %s" % type(packed).__name__)
+    H, W = _size(packed.size)
+    n, b = len(packed), packed.bits
+    if tuple(b.shape) != (n, H, (W + 31) // 32) or b.dtype != torch.int32 or not b.is_contiguous():
+        raise IndexError("PackedMasks of size %s with bits %s %s" % (packed.size, tuple(b.shape), b.dtype))
+    if n * W >= 1 << 40:
+        raise Ep24Error("ep24: encode: %d masks of width %d (EP24_E_UNSUPPORTED)" % (n, W))
+    _check_out(out, n)
+    _lib.require_gpu()
+    if not b.is_cuda or (out is not None and out[0].device != b.device):
+        raise Ep24Error("ep24: encode takes GPU tensors on one device (no CPU fallback on the product path)")
+    return _encode_packed(b, None, n, H, W, n * W, (H, W), out)
+
+
+def encode_buffer(buf, desc, out=None):
+    """The byte masks of ``decode_batch`` (``buf`` uint8 device buffer, ``desc [n, 6]`` = byte offset, h, w, ., ., row
+    stride) -> ``RunLengths`` whose ``size`` is the list of (h, w) per mask; ``encode_buffer(*decode_batch(segs, sizes))`` is
+    pycocotools' ``frPyObjects`` + ``merge``.  The masks are first packed per descriptor into ragged bit rows by a kernel, so
+    the run kernels have one input form; ``desc`` is read on the host (n rows) for the sizes.  ``out`` as for ``encode``."""
+    d = desc.cpu().numpy() if isinstance(desc, torch.Tensor) else np.asarray(desc)
+    if d.ndim != 2 or d.shape[1] != 6:
+        raise ValueError("desc is [n, 6]: byte offset, h, w, L, ray samples, row stride")
+    d = d.astype(np.int64)
+    if not isinstance(buf, torch.Tensor) or buf.dtype != torch.uint8 or buf.dim() != 1 or not buf.is_contiguous():
+        raise ValueError("buf is a contiguous 1-d uint8 tensor")
+    n = len(d)
+    off, H, W, ld = d[:, 0], d[:, 1], d[:, 2], d[:, 5]
+    if n and (H.min() < 1 or W.min() < 1 or (H * W).max() >= 1 << 31 or (ld < W).any() or off.min() < 0
+              or (off + (H - 1) * ld + W).max() > buf.numel()):
+        raise ValueError("desc names a mask outside the buffer, or h, w < 1, h * w >= 2^31, a row stride below w")
+    _check_out(out, n)
+    _lib.require_gpu()
+    if not buf.is_cuda or (out is not None and out[0].device != buf.device):
+        raise Ep24Error("ep24: encode_buffer takes GPU tensors on one device (no CPU fallback on the product path)")
+    dev = buf.device
+    sizes = [(int(h), int(w)) for h, w in zip(H, W)]
+    if n == 0:
+        return _encode_packed(buf, None, 0, 1, 1, 0, sizes, out)
+    words = np.concatenate([[0], np.cumsum(H * ((W + 31) // 32))])
+    cols = np.concatenate([[0], np.cumsum(W)])
+    tab = torch.from_numpy(np.ascontiguousarray(np.stack([words[:-1], H, W, cols[:-1]], 1))).to(dev)
+    desc_t = desc.to(dev).contiguous() if isinstance(desc, torch.Tensor) and desc.dtype == torch.int64 else torch.from_numpy(d).to(dev)
+    bits = torch.empty(int(words[-1]), dtype=torch.int32, device=dev)
+    call("rle_pack_bytes", ptr(buf), buf.numel(), ptr(desc_t), ptr(tab), n, int(H.max()), ptr(bits), stream_ptr())
+    return _encode_packed(bits, tab, n, int(H.max()), int(W.max()), int(cols[-1]), sizes, out)

@@ -14,6 +14,9 @@ import torch
 from . import _lib
 from ._lib import call, ptr, stream_ptr
 
+# the 80 "thing" category ids of COCO 2017 in ascending order: class index -> category id (the reference's :36-51)
+COCO_IDS = [i for i in range(1, 91) if i not in (12, 26, 29, 30, 45, 66, 68, 69, 71, 83)]
+
 _ROT = None
 
 

@@ -10,7 +10,9 @@ batch of annotations at a time (ep24.labels24 -> ep24_ray24 / ep24_hull_area24).
 reference's files (``%d`` + 50 x ``%0.4f`` in "Cord" mode, + 26 in "Radius" mode).  The masks come from one of two decoders:
 ``decoder="pycocotools"`` (the default, the reference's ``coco.annToMask`` on the host; the class raises ImportError with that
 name when it is constructed without the package) or ``decoder="gpu"`` (ep24.cocomask: the same masks decoded into the device
-buffer the rays read, no pycocotools, image sizes from the json's ``images``).
+buffer the rays read, no pycocotools, image sizes from the json's ``images``).  With the GPU decoder ``--save-rle FILE`` also writes
+``{annotation id: {"size": [h, w], "counts": str}}`` for every annotation decoded: the masks of that same device buffer, run-length
+encoded on the GPU (``cocomask.encode_buffer``) - a polygon annotation stored as the RLE pycocotools' ``frPyObjects`` + ``merge`` give.
 """
 import argparse
 import json
@@ -25,16 +27,16 @@ if _TOP not in sys.path:                  # `python datasets/labels_create_24p.p
     sys.path.insert(0, _TOP)
 import _path  # noqa: F401,E402
 from ep24 import cocomask, labels24  # noqa: E402
-
-# the 80 "thing" category ids of COCO 2017 in ascending order -> contiguous class index (:36-51)
-COCO_IDS = [i for i in range(1, 91) if i not in (12, 26, 29, 30, 45, 66, 68, 69, 71, 83)]
+from ep24.labels24 import COCO_IDS  # noqa: E402  (category ids in ascending order -> contiguous class index, :36-51)
 
 
 class Polygon_24:
     def __init__(self, mode="Cord", json_label_pth=None, image_data_pth=None, new_label_pth="./COCO_24p_label", batch=1024,
-                 decoder="pycocotools"):
+                 decoder="pycocotools", *, save_rle=None):
         if decoder not in ("pycocotools", "gpu"):
             raise ValueError("decoder is 'pycocotools' or 'gpu'")
+        if save_rle and decoder != "gpu":
+            raise ValueError("--save-rle encodes the masks of the GPU decoder's device buffer: it needs --decoder gpu")
         if decoder == "pycocotools":
             try:
                 from pycocotools.coco import COCO
@@ -43,6 +45,7 @@ class Polygon_24:
         self.mode, self.decoder = mode, decoder
         self.json_label_pth, self.image_data_pth, self.new_label_pth = json_label_pth, image_data_pth, new_label_pth
         self.batch = batch
+        self.save_rle, self.rle = save_rle, {}
         self.coco = COCO(self.json_label_pth) if decoder == "pycocotools" else None
         self.json_dict = self.load_label_json()
         self.label_dict_cord24, self.label_dict_radius = {}, {}
@@ -58,10 +61,12 @@ class Polygon_24:
     def _flush(self, pending, area_t_low, area_t_high):
         if not pending:
             return
-        names, cls, centres, masks, areas, shapes = zip(*pending)
+        names, cls, centres, masks, areas, shapes, ids = zip(*pending)
         if self.decoder == "gpu":                             # masks are segmentations: decoded where the rays read them
             buf, desc = cocomask.decode_batch(list(masks), list(shapes))
             pts, rad = labels24.rays_from_buffer(buf, desc, centres)
+            if self.save_rle:
+                self.rle.update(zip((str(i) for i in ids), cocomask.encode_buffer(buf, desc).to_coco()))
         else:
             pts, rad = labels24.rays_batch(list(masks), centres)
         hull = labels24.hull_areas(pts)
@@ -90,10 +95,13 @@ class Polygon_24:
                 assert shape == tuple(sizes.get(anno["image_id"], shape))
             cx = anno["bbox"][0] + anno["bbox"][2] / 2
             cy = anno["bbox"][1] + anno["bbox"][3] / 2
-            pending.append((name, self.coco_id2idx[str(anno["category_id"])], (cx, cy), mask, anno["area"], shape))
+            pending.append((name, self.coco_id2idx[str(anno["category_id"])], (cx, cy), mask, anno["area"], shape, anno.get("id")))
             if len(pending) >= self.batch:
                 self._flush(pending, area_t_low, area_t_high)
         self._flush(pending, area_t_low, area_t_high)
+        if self.save_rle:
+            with open(self.save_rle, "w") as f:
+                json.dump(self.rle, f)
         return self.label_dict_cord24, self.label_dict_radius
 
     def save_24r_to_txt(self):
@@ -112,7 +120,11 @@ if __name__ == "__main__":
     ap.add_argument("--mode", default="Cord", choices=["Cord", "Radius"])
     ap.add_argument("--decoder", default="pycocotools", choices=["pycocotools", "gpu"],
                     help="where annToMask runs: pycocotools on the host, or the ep24.cocomask kernels (no pycocotools needed)")
+    ap.add_argument("--save-rle", default=None, metavar="FILE",
+                    help="with --decoder gpu: also write {annotation id: {size, counts}}, the decoded masks as COCO RLE")
     a = ap.parse_args()
-    polygon = Polygon_24(a.mode, a.json, a.images, a.out, decoder=a.decoder)
+    if a.save_rle and a.decoder != "gpu":
+        ap.error("--save-rle encodes the masks of the GPU decoder's device buffer: it needs --decoder gpu")
+    polygon = Polygon_24(a.mode, a.json, a.images, a.out, decoder=a.decoder, save_rle=a.save_rle)
     polygon.json_anno_process()
     polygon.save_24r_to_txt()

@@ -9,7 +9,8 @@ save every image with its 24-point detections drawn on it.
 ``ep24.draw.draw_detections`` on the ORIGINAL image with the letterbox ratio - the reference's ``Evaluator.eval`` /
 ``save_eval_results`` / ``vis`` (:266-367) without the host-side OpenCV.  Results go to ``<output_dir>/<timestamp>/``: the drawn
 image under its own name, ``<name>.dets.npy`` with the ``[n, 29]`` float32 rows beside it, and one ``detections.json`` (file, size,
-ratio, count).  ``.npy`` (uint8 HWC) and binary PPM are read and written natively; JPEG / PNG when PIL is installed.
+ratio, count).  ``--save-segm FILE`` also writes every detection of the run as a COCO "segm" result (``ep24.results``: the polygon
+rasterised on the original image and run-length encoded on the GPU).  ``.npy`` (uint8 HWC) and binary PPM are read and written natively; JPEG / PNG when PIL is installed.
 """
 import argparse
 import json
@@ -140,6 +141,11 @@ class Evaluator:
         self.save_folder = os.path.join(args.output_dir or self.exp.output_dir, time.strftime("%Y_%m_%d_%H_%M_%S", time.localtime()))
         os.makedirs(self.save_folder, exist_ok=True)
         records = []
+        segm = None
+        if args.save_segm:
+            from ep24.labels24 import COCO_IDS
+            from ep24.results import SegmResults
+            segm = SegmResults(COCO_IDS if args.segm_category_ids == "coco" else None)
         step = max(int(args.batch_size), 1)
         for lo in range(0, len(self.file_list), step):
             names = self.file_list[lo:lo + step]
@@ -155,10 +161,16 @@ class Evaluator:
                 np.save(os.path.join(self.save_folder, name + ".dets.npy"), rows)
                 records.append({"file": name, "height": int(img.shape[0]), "width": int(img.shape[1]), "ratio": float(ratio),
                                 "count": int(rows.shape[0])})
+                if segm is not None:
+                    stem = os.path.splitext(name)[0]
+                    segm.add(int(stem) if stem.isascii() and stem.isdigit() else stem, dets, ratio, (int(img.shape[0]), int(img.shape[1])))
                 print("%s: %d detections" % (name, rows.shape[0]))
         with open(os.path.join(self.save_folder, "detections.json"), "w") as fh:
             json.dump({"input_size": list(self.input_size), "conf": args.conf, "nms": args.nms, "nms_iou": args.nms_iou,
                        "draw_conf": args.draw_conf, "images": records}, fh, indent=1)
+        if segm is not None:
+            segm.dump(args.save_segm)
+            print("saved %d segm results to %s" % (len(segm), args.save_segm))
         print("saved %d images to %s" % (len(records), self.save_folder))
         return self.save_folder
 
@@ -181,6 +193,10 @@ def make_parser():
     p.add_argument("--fill-alpha", default=0, type=int, help="0..255: blend the class colour over the polygon's inside (0 = outline only)")
     p.add_argument("--show-scores", action="store_true", help="append the score's two decimals to the label")
     p.add_argument("--class-names", default=None, type=str, help="a file with one class name per line (default: the class index)")
+    p.add_argument("--save-segm", default=None, type=str, metavar="FILE", help="write every detection as a COCO segm result (RLE mask of "
+                   "its polygon on the original image, score, bbox, area) to this json file")
+    p.add_argument("--segm-category-ids", default="index", choices=["coco", "index"], help="--save-segm: category_id is COCO's id of "
+                   "the class (80 classes) or the class index")
     p.add_argument("--device", default="cuda", type=str, help="cuda or cuda:N (the ep24 path has no CPU fallback: cpu is refused)")
     return p
 

@@ -803,7 +803,36 @@ int ep24_cocomask_rle(uint8_t* masks, int64_t total, const int64_t* desc, const 
                       int max_w, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
- * N1  input pipeline (yolox_24p/datasets/data_augment.py:109-174)
+ * E5  instance masks -> COCO run lengths (csrc/rle.hip; ep24.cocomask.encode).  pycocotools' rleEncode: the mask
+ *     is walked column-major (p = x * H + y) from a previous value of 0, every change of value closes a run, the end closes the last;
+ *     the first run is of zeros (0 when pixel (0, 0) is set), an all-zero mask is [H * W], an all-one mask [0, H * W].  Input: packed
+ *     masks as in E2.  Integer work only, no atomics, every result a bit-exact function of the inputs; nothing allocates or synchronises.
+ *   The batch is N masks of one size H x W behind each other (tab == NULL; column tables at n * W), or masks of their own sizes
+ *     named by tab[N][4] int64 = {first uint32 word of the mask in bits, H, W, first entry of the mask in the column table}; then
+ *     the H and W arguments are the largest of the table.  A table row with H or W <= 0 or H * W >= 2^31 is skipped (one run of 0).
+ *   N < 0, H or W <= 0, H * W >= 2^31: EP24_E_UNSUPPORTED.  A null pointer with N > 0: EP24_E_ARG.  A grid axis over N is cut into
+ *     launches of 65 535 inside the call.
+ * ep24_rle_pack_bytes: the byte masks of ep24_ray24's buffer and desc[N][6] (non-zero = set) -> the packed rows tab names; H and W
+ *   are tab's and must be desc's, max_h the largest H.  A mask that does not lie inside [0, total) is left unwritten.
+ * ep24_rle_count: colcnt[mask's first entry + x] int32 = the transitions in column x (the pixel before (x, 0) is (x - 1, H - 1)).
+ * ep24_rle_scan: colcnt -> per mask the exclusive prefix over its columns, in place; offsets[N + 1] int64 = the exclusive prefix
+ *   of runs[n] = transitions + 1 over the masks, in index order.  N = 0 writes offsets[0] = 0.
+ * ep24_rle_emit: ends[offsets[n] + j] int32 = the position of mask n's transition j, j < runs[n] - 1 (entry runs[n] - 1 is not
+ *   written); cap = the entries ends can hold: nothing is written at or beyond it, or outside the mask's own range.
+ * ep24_rle_counts: counts[i] int32, i < min(total, offsets[N]) = ends[i] - ends[i - 1], with 0 before a mask's first end and H * W
+ *   as its last; counts and ends are different buffers.
+ * ------------------------------------------------------------------------------------------------ */
+int ep24_rle_pack_bytes(const uint8_t* masks, int64_t total, const int64_t* desc, const int64_t* tab, int N, int max_h,
+                        uint32_t* bits, void* stream);
+int ep24_rle_count(const uint32_t* bits, const int64_t* tab, int N, int H, int W, int32_t* colcnt, void* stream);
+int ep24_rle_scan(int32_t* colcnt, const int64_t* tab, int N, int H, int W, int64_t* offsets, void* stream);
+int ep24_rle_emit(const uint32_t* bits, const int64_t* tab, int N, int H, int W, const int32_t* colprefix, const int64_t* offsets,
+                  int32_t* ends, int64_t cap, void* stream);
+int ep24_rle_counts(const int32_t* ends, const int64_t* offsets, const int64_t* tab, int N, int H, int W, int64_t total,
+                    int32_t* counts, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * N1 input pipeline (yolox_24p/datasets/data_augment.py:109-174)
  * ------------------------------------------------------------------------------------------------ */
 /* preproc for n images (n <= 65535): images = raw uint8 HWC sources in one device buffer; desc[n][6] int64 =
  * {byte offset, h, w, row stride in bytes, rh = int(h*r), rw = int(w*r)} with r = min(S_h/h, S_w/w) (:118-123);
