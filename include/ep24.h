@@ -832,6 +832,55 @@ int ep24_rle_counts(const int32_t* ends, const int64_t* offsets, const int64_t* 
                     int32_t* counts, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * E6  COCO "segm" evaluation on instance masks (csrc/segmeval.hip; ep24.segmeval.SegmEvaluator): pycocotools'
+ *     rleIou, evaluateImg and accumulate with crowd GTs, ignore flags, area ranges and several maxDets.  Packed masks as in E2, named
+ *     by tab[N][4] int64 = {first uint32 word of the mask in bits, H, W, unused} as for ep24_rle_count.  Nothing allocates, frees or
+ *     synchronises; the only atomics are the integer sums into npig; every result is a bit-exact function of the inputs.
+ * ep24_segm_mask_stats: bbox[N][4] and area[N] int32 with E2's meaning ((x0, y0, x1, y1) of the set pixels, (W, H, -1, -1) for an empty
+ *   mask, the popcount).  Every output word is written; a table row with a negative first word, H or W <= 0 or H * W >= 2^31 reads no
+ *   mask word and gives (0, 0, -1, -1) and 0.
+ * ep24_segm_iou: grp[J][8] int64, one row per (image, category) = {H, W, first GT mask, G, first DT mask, D, first entry in iou, 0};
+ *   mask indices point into tab, bbox, area (N rows) and gt_crowd (uint8 per mask, read for GT masks only).  The first entries must be
+ *   the running sum of G * D over the rows (from any base) and pairs that sum: one wave per pair finds its row by a binary search.
+ *   iou[first entry + d * G + g] double, detection-major as pycocotools holds it: with inter = popcount(GT_g & DT_d) over the rows and
+ *   words where the two boxes overlap (disjoint boxes read no mask word), 0.0 if inter == 0, else inter / area(DT_d) for a crowd GT and
+ *   inter / (area_g + area_d - inter) otherwise - one correctly rounded double division of exact integers (rleIou).  inter (nullable)
+ *   int64 receives the counts at the same indices.  G == 0 or D == 0 writes nothing.  The masks of a group have the group's H and W:
+ *   a pair whose table rows say otherwise is written as 0 without reading a mask word; a row that names masks outside [0, N) writes
+ *   nothing.  More than 2^24 pairs are cut into several launches inside the call.
+ * ep24_segm_match: one wave per row of mgrp[J][8] int64 = {first GT, G, first detection, D (<= 128), first entry in iou, class, image
+ *   sequence number (< 2^25), 0}.  GT indices address gt_crowd, gt_ignore0 (uint8: the annotation's ignore OR iscrowd, the host's OR)
+ *   gt_area (double: the annotation's area field) and scratch; detection indices address dt_area (double), dt_rank (int32: the dense
+ *   rank of the score among the run's distinct scores, 0 = highest) and the records.  Detections stand in the order the host fixed
+ *   (score descending, input order ascending).  For every area range a < NA <= 4 of area_rng[NA][2] double and every threshold t of
+ *   iou_thr[10] double, evaluateImg: GT g is ignored iff ignore0 || gt_area < lo || gt_area > hi; the GTs are taken in a stable order
+ *   with the non-ignored first; per detection, best = min(thr, 1 - 1e-10), a GT already matched at (a, t) is skipped unless it is
+ *   crowd, the walk stops at the first ignored GT once a non-ignored match is held, a GT with iou >= best becomes the match (equal
+ *   IoUs go to the later GT); a matched detection inherits the GT's ignore flag, an unmatched one is ignored iff dt_area lies outside
+ *   the range.  Record n = the detection's index: rec_m[n][NA] int32 = 10 TP bits | 10 ignore bits << 16, rec_key[n] =
+ *   dt_rank << 32 | sequence << 7 | position in the group, rec_cls[n] = class: ep24_eval_sort's ascending order of (class, key) is
+ *   pycocotools' (class, score descending, image, position).  npig[num_classes][NA] int32 += the non-ignored GTs (the caller zeroes
+ *   it once per evaluation).  Scratch: one int64 per GT of the call, indexed as gt_area is (only groups with G > 64 touch it; there
+ *   is no other cap on G).  A row with D > 128, a negative count or index or a class outside [0, num_classes) is skipped.
+ * ep24_segm_accumulate: over the n records in the order ep24_eval_sort gave, for every class k, area range a and max_dets[m] (int32
+ *   [NM], NM <= 4): only records whose position is < max_dets[m] count, a record ignored at t is neither TP nor FP at t;
+ *   precision[10][101][K][NA][NM] and recall[10][K][NA][NM] double with the expressions of ep24_eval_accumulate - tp / (fp + tp + eps),
+ *   the envelope from the right, the left search over recall = tp / npig - and -1 where npig[k][a] == 0.  rec_thr[101] double;
+ *   cls_range [K][2] int64, ctp_scratch [NA * NM][n] int32, env_scratch [NA * NM][n] double.  K <= 65535.
+ * ------------------------------------------------------------------------------------------------ */
+int ep24_segm_mask_stats(const uint32_t* bits, const int64_t* tab, int N, int32_t* bbox, int32_t* area, void* stream);
+int ep24_segm_iou(const uint32_t* bits, const int64_t* tab, int N, const int32_t* bbox, const int32_t* area,
+                  const uint8_t* gt_crowd, const int64_t* grp, int J, int64_t pairs, double* iou, int64_t* inter, void* stream);
+int ep24_segm_match(const int64_t* mgrp, int J, const double* iou, const uint8_t* gt_crowd, const uint8_t* gt_ignore0,
+                    const double* gt_area, const double* dt_area, const int32_t* dt_rank, const double* area_rng, int NA,
+                    const double* iou_thr, int num_classes, int64_t* scratch, int32_t* rec_m, int64_t* rec_key, int32_t* rec_cls,
+                    int32_t* npig, void* stream);
+int ep24_segm_accumulate(const int32_t* order, const int64_t* rec_key, const int32_t* rec_cls, const int32_t* rec_m, int64_t n,
+                         const int32_t* npig, int num_classes, int NA, const int32_t* max_dets, int NM, const double* rec_thr,
+                         int64_t* cls_range, int32_t* ctp_scratch, double* env_scratch, double* precision, double* recall,
+                         void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * N1 input pipeline (yolox_24p/datasets/data_augment.py:109-174)
  * ------------------------------------------------------------------------------------------------ */
 /* preproc for n images (n <= 65535): images = raw uint8 HWC sources in one device buffer; desc[n][6] int64 =
