@@ -2,7 +2,8 @@
 
 The model's product is a star polygon per object: a centre and 24 radii on the 15-degree rays.  ``detection_polygons``
 turns detection rows into vertices, ``rasterize`` fills them into bit-packed instance masks (what a COCO "segm" evaluation
-or any downstream user of an instance detector consumes), ``mask_iou`` compares two sets of masks by AND + popcount.
+or any downstream user of an instance detector consumes), ``mask_iou`` compares two sets of masks by AND + popcount,
+``boundary`` keeps the band of a mask that Boundary IoU compares (csrc/boundary.hip).
 
 Packed format: ``bits`` int32 ``[N, H, ceil(W / 32)]`` holding uint32 words (pixel x is bit ``x & 31`` of word ``x >> 5``,
 bits at x >= W are zero), ``bbox`` int32 ``[N, 4]`` = (x0, y0, x1, y1), the smallest and largest set pixel, or
@@ -13,6 +14,8 @@ Pixel rule: the centre of pixel (x, y) is the point (x, y)
 pixel x is set iff an odd number of counting edges have ``x < xc``.  Left and top boundary pixels are in, right and bottom
 ones out (cv2.fillPoly sets all four).  All compute runs as HIP kernels; torch only allocates and copies.
 """
+import math
+
 import torch
 
 from . import _lib
@@ -140,6 +143,33 @@ def mask_iou(a, b):
     iou = torch.empty(G, D, dtype=torch.float64, device=dev)
     call("mask_iou", ptr(a.bits), ptr(a.bbox), ptr(a.area), G, ptr(b.bits), ptr(b.bbox), ptr(b.area), D, H, W, ptr(inter), ptr(iou), stream_ptr())
     return inter, iou
+
+
+def boundary(packed, d=None, dilation_ratio=0.02):
+    """``PackedMasks`` -> ``PackedMasks`` of the boundary bands of Boundary IoU (include/ep24.h section E7): the mask pixels within
+    ``d`` pixels of the mask's outside, the outside of the image included (``mask & ~erode(mask, d)``, a (2d + 1)-square erosion).
+    ``d`` defaults to ``max(1, round(dilation_ratio * diagonal of packed.size))``; ``bbox`` and ``area`` are the bands'."""
+    _check_packed(packed, "boundary")
+    H, W = _size(packed.size)
+    if d is None:
+        if not (math.isfinite(dilation_ratio) and dilation_ratio > 0):
+            raise ValueError("dilation_ratio %r: a positive finite number" % (dilation_ratio,))
+        d = max(1, int(round(dilation_ratio * math.sqrt(H * H + W * W))))
+    d = int(d)
+    if d < 1:
+        raise Ep24Error("ep24: boundary radius d=%d: at least 1 (EP24_E_UNSUPPORTED)" % d)
+    N, dev = len(packed), packed.bits.device
+    out = _alloc(N, H, W, dev)
+    if N == 0:
+        return out
+    WW = (W + 31) // 32
+    tab = torch.zeros(N, 4, dtype=torch.int64)                                       # the statistics kernel names its masks by a table
+    tab[:, 0], tab[:, 1], tab[:, 2] = torch.arange(N, dtype=torch.int64) * (H * WW), H, W
+    tab = tab.to(dev)
+    s = stream_ptr()
+    call("mask_boundary", ptr(packed.bits), None, N, H, W, min(d, max(H, W)), ptr(out.bits), s)
+    call("segm_mask_stats", ptr(out.bits), ptr(tab), N, ptr(out.bbox), ptr(out.area), s)
+    return out
 
 
 def detections_to_masks(dets, ratio, image_hw):

@@ -11,8 +11,16 @@ differ only beyond fp32 keep pycocotools' order in the 64-bit sort key.  The ima
 ``ep24_segm_iou`` and ``ep24_segm_match`` run on the device, at the end ``ep24_eval_sort`` and ``ep24_segm_accumulate``, and the
 precision / recall tables come back in one copy.  As in pycocotools' ``loadRes`` a result's area is the pixel count of its mask;
 a GT's area is the annotation's ``area`` field and its ignore flag the annotation's ``ignore`` OR ``iscrowd``.
+
+``SegmEvaluator(gt, iou_type="boundary")`` scores the same results by Boundary IoU (Cheng et al., CVPR 2021; include/ep24.h section
+E7): every pair's IoU becomes ``min(mask IoU, IoU of the two masks' boundary bands)``, the band being the mask pixels within
+``d = max(1, round(dilation_ratio * image diagonal))`` pixels of the mask's outside.  Per chunk ``ep24_mask_boundary`` writes the
+bands into a second packed buffer (each mask with its own image's ``d``), ``ep24_segm_mask_stats`` and ``ep24_segm_iou`` run on them
+as on the masks (a crowd GT divides by the area of the detection's band) and ``ep24_segm_iou_min`` folds the second IoU table into
+the first; the matcher, the areas of the area ranges (the MASK's pixel count) and everything after are those of "segm".
 """
 import json
+import math
 
 import numpy as np
 import torch
@@ -29,6 +37,12 @@ MAX_AREA_RANGES = 4
 MAX_MAX_DETS = 4
 MAX_IMAGES = 1 << 25
 MAX_CLASSES = 65535
+IOU_TYPES = ("segm", "boundary")
+
+
+def dilation(h, w, ratio=0.02):
+    """The radius of the boundary band of an ``h x w`` image: ``max(1, round(ratio * diagonal))``, Python's round (half to even)."""
+    return max(1, int(round(ratio * math.sqrt(h * h + w * w))))
 
 
 def _load(obj, what):
@@ -184,9 +198,16 @@ class SegmEvaluator:
     instances dict or its path.  ``add_results(results)``: a list of result dicts (``image_id``, ``category_id``, ``score``,
     ``segmentation`` = an RLE dict, compressed or not, or a list of polygons), a path, or a ``SegmResults``; several calls add up.
     ``evaluate()`` -> dict with ``stats`` (the 12 numbers in pycocotools' order), ``precision`` [10, 101, K, A, M], ``recall``
-    [10, K, A, M] and ``per_class_AP`` (range 0, the last maxDets); ``summary`` holds the printed lines."""
+    [10, K, A, M] and ``per_class_AP`` (range 0, the last maxDets); ``summary`` holds the printed lines.  ``iou_type="boundary"``
+    with ``dilation_ratio`` (0.02): Boundary IoU in place of the mask IoU, everything else - and the summary's text - unchanged."""
 
-    def __init__(self, gt, max_dets=(1, 10, 100), area_ranges=AREA_RANGES, device="cuda:0", chunk_bytes=256 << 20, area_labels=None):
+    def __init__(self, gt, max_dets=(1, 10, 100), area_ranges=AREA_RANGES, device="cuda:0", chunk_bytes=256 << 20, area_labels=None,
+                 iou_type="segm", dilation_ratio=0.02):
+        if iou_type not in IOU_TYPES:
+            raise ValueError("iou_type %r: one of %s" % (iou_type, IOU_TYPES))
+        if isinstance(dilation_ratio, bool) or not isinstance(dilation_ratio, (int, float)) or not (math.isfinite(dilation_ratio) and dilation_ratio > 0):
+            raise ValueError("dilation_ratio %r: a positive finite number" % (dilation_ratio,))
+        self.iou_type, self.dilation_ratio = iou_type, float(dilation_ratio)
         self.max_dets = [int(m) for m in max_dets]
         self.area_ranges = np.asarray(area_ranges, dtype=np.float64).reshape(-1, 2)
         if not 1 <= len(self.max_dets) <= MAX_MAX_DETS or min(self.max_dets) < 1 or max(self.max_dets) > MAX_DETS_LIMIT:
@@ -238,7 +259,9 @@ class SegmEvaluator:
         words = np.concatenate([[0], np.cumsum(hw[:, 0] * ((hw[:, 1] + 31) // 32))])
         if int(words[-1]) >= 1 << 40 or n >= 1 << 31:
             raise Ep24Error("ep24: a chunk of %d masks, %d words: lower chunk_bytes (EP24_E_UNSUPPORTED)" % (n, int(words[-1])))
-        tab = torch.from_numpy(np.ascontiguousarray(np.stack([words[:-1], hw[:, 0], hw[:, 1], np.zeros(n, dtype=np.int64)], 1))).to(dev)
+        boundary = self.iou_type == "boundary"
+        rad = np.array([dilation(int(h), int(w), self.dilation_ratio) for h, w in hw], dtype=np.int64) if boundary else np.zeros(n, dtype=np.int64)
+        tab = torch.from_numpy(np.ascontiguousarray(np.stack([words[:-1], hw[:, 0], hw[:, 1], rad], 1))).to(dev)
         bits = torch.empty(int(words[-1]), dtype=torch.int32, device=dev)
         call("rle_pack_bytes", ptr(buf), buf.numel(), ptr(desc), ptr(tab), n, int(hw[:, 0].max()), ptr(bits), s)
         bbox = torch.empty(n, 4, dtype=torch.int32, device=dev)
@@ -262,6 +285,13 @@ class SegmEvaluator:
         iou = torch.empty(max(pairs, 1), dtype=torch.float64, device=dev)
         scratch = torch.empty(max(nG, 1), dtype=torch.int64, device=dev)
         call("segm_iou", ptr(bits), ptr(tab), n, ptr(bbox), ptr(area), ptr(flags), ptr(tabs), J, pairs, ptr(iou), None, s)
+        if boundary:                                                                 # the bands' IoU, then the smaller of the two
+            band = torch.empty_like(bits)
+            band_bbox, band_area, band_iou = torch.empty_like(bbox), torch.empty_like(area), torch.empty_like(iou)
+            call("mask_boundary", ptr(bits), ptr(tab), n, int(hw[:, 0].max()), int(hw[:, 1].max()), 0, ptr(band), s)
+            call("segm_mask_stats", ptr(band), ptr(tab), n, ptr(band_bbox), ptr(band_area), s)
+            call("segm_iou", ptr(band), ptr(tab), n, ptr(band_bbox), ptr(band_area), ptr(flags), ptr(tabs), J, pairs, ptr(band_iou), None, s)
+            call("segm_iou_min", ptr(iou), ptr(band_iou), pairs, s)
         NA = len(self.area_ranges)
         call("segm_match", ptr(tabs, J * 8), J, ptr(iou), ptr(flags), ptr(flags, len(crowd)), ptr(gt_area), ptr(dt_area), ptr(dt_rank),
              ptr(rng), NA, ptr(thr), len(gt["cat_ids"]), ptr(scratch), ptr(rec["m"], da0 * NA), ptr(rec["key"], da0), ptr(rec["cls"], da0),
@@ -313,5 +343,6 @@ class SegmEvaluator:
         self.summary = "\n".join(lines) + "\n"
         self.stats = {"stats": stats, "precision": precision, "recall": recall, "per_class_AP": np.array(per_class),
                       "category_ids": list(self.gt["cat_ids"]), "images": len(self.gt["img_ids"]), "results": len(self.results),
-                      "dropped": plan["dropped"], "records": n, "chunks": self.chunks}
+                      "dropped": plan["dropped"], "records": n, "chunks": self.chunks, "iou_type": self.iou_type,
+                      "dilation_ratio": self.dilation_ratio}
         return self.stats

@@ -881,6 +881,26 @@ int ep24_segm_accumulate(const int32_t* order, const int64_t* rec_key, const int
                          void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * E7  boundary bands for Boundary IoU (csrc/boundary.hip; ep24.masks.boundary, SegmEvaluator(iou_type="boundary")).
+ *     For a mask M of an H x W image and a radius d >= 1: erode(M, d) sets pixel (x, y) iff every pixel (x', y') with |x' - x| <= d and
+ *     |y' - y| <= d is set in M, pixels outside the image counting as not set (d iterations of a 3 x 3 erosion on the zero-framed mask);
+ *     boundary(M, d) = M & ~erode(M, d).  Boundary IoU of a pair is min(rleIou of the masks, rleIou of their bands), the radius being
+ *     max(1, round(0.02 * the image's diagonal)): the host's formula, never the object's size.  Packed masks as in E2.  Integer work
+ *     only, no atomics, nothing allocates or synchronises; every result is a bit-exact function of the inputs.
+ * ep24_mask_boundary: out = boundary(bits, d) at the same word offsets as bits.  tab == NULL: N masks of one size H x W behind each
+ *   other, one radius d for all.  Otherwise tab[N][4] int64 = {first uint32 word of the mask in bits and out, H, W, d}; the H and W
+ *   arguments are then the largest of the table and the d argument is ignored.  Every word of out that belongs to a valid mask is
+ *   written by the call (no memset needed), the bits at x >= W as zero; nothing else is written.  d >= max(H, W) gives out == bits (the
+ *   radius is clamped, not walked).  A table row with a negative first word, H or W <= 0, H * W >= 2^31 or d < 1 is skipped and writes
+ *   nothing.  N < 0, H or W <= 0 (N > 0), H * W >= 2^31, d < 1 without a table: EP24_E_UNSUPPORTED.  A null bits or out with N > 0, or
+ *   out == bits: EP24_E_ARG.  N == 0 writes nothing.  A grid axis over N is cut into launches of 65 535 inside the call.
+ * ep24_segm_iou_min: iou[i] = other[i] < iou[i] ? other[i] : iou[i], i < n (finite, non-negative values; n == 0 is EP24_OK): the min of
+ *   the two IoU tables of ep24_segm_iou, kept behind the ABI like every other piece of compute.
+ * ------------------------------------------------------------------------------------------------ */
+int ep24_mask_boundary(const uint32_t* bits, const int64_t* tab, int N, int H, int W, int d, uint32_t* out, void* stream);
+int ep24_segm_iou_min(double* iou, const double* other, int64_t n, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * N1 input pipeline (yolox_24p/datasets/data_augment.py:109-174)
  * ------------------------------------------------------------------------------------------------ */
 /* preproc for n images (n <= 65535): images = raw uint8 HWC sources in one device buffer; desc[n][6] int64 =
