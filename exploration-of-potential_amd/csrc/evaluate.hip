@@ -7,18 +7,20 @@
 //                 p asc) in global scratch, then one wave per class segment greedily matches the first max_dets detections
 //                 against the class's GTs for all 10 IoU thresholds and appends one record per detection
 //   eval_sort     stable LSD radix sort of the records by (class, score desc, image seq, rank)
-//   eval_accumulate  one workgroup per class: cumulative TP / FP counts, precision envelope and the 101 recall look-ups in double
+//   eval_accumulate  the accumulate kernel of accumulate.h (shared with segmeval.hip) for one area range and one maxDets: one
+//                 workgroup per class finds its records in the sorted order, then cumulative TP / FP counts, precision envelope
+//                 and the 101 recall look-ups in double
 //
 // Determinism: the only atomics are integer ones whose order does not matter - the GT count per class (a sum) and the
 // append offset of a class segment's records (the sort key fixes the final order; (class, seq, rank) is unique).
 // No floating-point atomics anywhere.
+#include "accumulate.h"
 #include "geom.h"
 #include "poly24.h"
 
 namespace {
 
 constexpr int EV_T = 10;             // IoU thresholds
-constexpr int EV_R = 101;            // recall thresholds
 constexpr int EV_MAX_L = 256;        // GT rows per image
 constexpr int EV_MAX_DETS = 128;     // detections per (image, class): the rank takes 7 bits of the record key
 constexpr int EV_NONE = 0xFFFF;      // class field of a detection whose class is outside [0, C): sorted last, never recorded
@@ -329,11 +331,7 @@ __global__ __launch_bounds__(1024) void scan_excl_kernel(int32_t* a, int64_t m) 
             v[q] = i < m ? a[i] : 0;
             s += v[q];
         }
-        int incl = s;
-        for (int o = 1; o < 64; o <<= 1) {
-            const int x = __shfl_up(incl, o, 64);
-            if (lane >= o) incl += x;
-        }
+        const int incl = wave_incl_sum(s, lane);
         if (lane == 63) ws[w] = incl;
         __syncthreads();
         int pre = carry_sh;
@@ -394,113 +392,6 @@ __global__ __launch_bounds__(256) void radix_scatter_kernel(const int64_t* key, 
         }
         __syncthreads();
         off[tid] += wc[0][tid] + wc[1][tid] + wc[2][tid] + wc[3][tid];
-        __syncthreads();
-    }
-}
-
-// ---------------------------------------------------------------------------------------------- accumulation
-__global__ __launch_bounds__(256) void class_range_kernel(const int32_t* order, const int32_t* rec_cls, int64_t n, int C,
-                                                          int64_t* range) {
-    for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < n; j += (int64_t)gridDim.x * 256) {
-        const int c = rec_cls[order[j]];
-        if (j == 0 || rec_cls[order[j - 1]] != c) range[2 * c] = j;
-        if (j == n - 1 || rec_cls[order[j + 1]] != c) range[2 * c + 1] = j + 1;
-    }
-}
-
-// one workgroup per class k: pycocotools accumulate for one area range and one maxDets
-__global__ __launch_bounds__(256) void accumulate_kernel(const int32_t* order, const int32_t* rec_tp, const int64_t* range,
-                                                         const int32_t* npig, int C, const double* rthr, int32_t* ctp, double* env,
-                                                         double* precision, double* recall) {
-    __shared__ int wsi[4];
-    __shared__ double wsd[4];
-    __shared__ int carry_i;
-    __shared__ double carry_d;
-    const int k = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int np = npig[k];
-    if (np == 0) {                                        // no GT of this class: excluded (-1), as pycocotools
-        for (int i = tid; i < EV_T * EV_R; i += 256) precision[(int64_t)i * C + k] = -1.0;
-        if (tid < EV_T) recall[tid * C + k] = -1.0;
-        return;
-    }
-    const int64_t s = range[2 * k], n = range[2 * k + 1] - s;
-    const double dnp = (double)np;
-    for (int t = 0; t < EV_T; ++t) {
-        // tp_j = inclusive count of TPs at threshold t; pr_j = tp / (tp + fp + eps) with tp + fp = j + 1
-        if (tid == 0) carry_i = 0;
-        __syncthreads();
-        for (int64_t b0 = 0; b0 < n; b0 += 1024) {
-            int v[4], sum = 0;
-            for (int q = 0; q < 4; ++q) {
-                const int64_t j = b0 + tid * 4 + q;
-                v[q] = j < n ? (rec_tp[order[s + j]] >> t) & 1 : 0;
-                sum += v[q];
-            }
-            int incl = sum;
-            for (int o = 1; o < 64; o <<= 1) {
-                const int x = __shfl_up(incl, o, 64);
-                if (lane >= o) incl += x;
-            }
-            if (lane == 63) wsi[w] = incl;
-            __syncthreads();
-            int run = carry_i + incl - sum;
-            for (int q = 0; q < w; ++q) run += wsi[q];
-            for (int q = 0; q < 4; ++q) {
-                const int64_t j = b0 + tid * 4 + q;
-                run += v[q];
-                if (j < n) {
-                    ctp[s + j] = run;
-                    env[s + j] = (double)run / ((double)(j + 1) + 2.220446049250313e-16);
-                }
-            }
-            __syncthreads();
-            if (tid == 0) carry_i += wsi[0] + wsi[1] + wsi[2] + wsi[3];
-            __syncthreads();
-        }
-        // envelope: pr_j = max over i >= j (chunks from the right)
-        if (tid == 0) carry_d = 0.0;
-        __syncthreads();
-        const int64_t nch = (n + 1023) / 1024;
-        for (int64_t ch = nch - 1; ch >= 0; --ch) {
-            const int64_t b0 = ch * 1024;
-            double v[4];
-            double mx = 0.0;
-            for (int q = 3; q >= 0; --q) {
-                const int64_t j = b0 + tid * 4 + q;
-                v[q] = j < n ? env[s + j] : 0.0;
-                mx = fmax(mx, v[q]);
-            }
-            double incl = mx;                             // suffix max over this lane and the lanes above it
-            for (int o = 1; o < 64; o <<= 1) {
-                const double x = __shfl_down(incl, o, 64);
-                if (lane + o < 64) incl = fmax(incl, x);
-            }
-            if (lane == 0) wsd[w] = incl;
-            __syncthreads();
-            double run = carry_d;
-            for (int q = w + 1; q < 4; ++q) run = fmax(run, wsd[q]);
-            const double above = __shfl_down(incl, 1, 64);
-            if (lane < 63) run = fmax(run, above);
-            for (int q = 3; q >= 0; --q) {
-                const int64_t j = b0 + tid * 4 + q;
-                run = fmax(run, v[q]);
-                if (j < n) env[s + j] = run;
-            }
-            __syncthreads();
-            if (tid == 0) carry_d = fmax(fmax(fmax(carry_d, wsd[0]), fmax(wsd[1], wsd[2])), wsd[3]);
-            __syncthreads();
-        }
-        // the 101 recall thresholds: precision at the first j with rc_j >= r (searchsorted 'left'), 0 past the end
-        if (tid < EV_R) {
-            const double rt = rthr[tid];
-            int64_t lo = 0, hi = n;
-            while (lo < hi) {
-                const int64_t mid = (lo + hi) >> 1;
-                if ((double)ctp[s + mid] / dnp >= rt) hi = mid; else lo = mid + 1;
-            }
-            precision[((int64_t)t * EV_R + tid) * C + k] = lo < n ? env[s + lo] : 0.0;
-        }
-        if (tid == 0) recall[t * C + k] = n ? (double)ctp[s + n - 1] / dnp : 0.0;
         __syncthreads();
     }
 }
@@ -584,17 +475,11 @@ extern "C" int ep24_eval_sort(const int64_t* key, const int32_t* cls, int64_t n,
 extern "C" int ep24_eval_accumulate(const int32_t* order, const int32_t* rec_cls, const int32_t* rec_tp, int64_t n, const int32_t* npig,
                                     int num_classes, const double* rec_thr, int64_t* cls_range, int32_t* ctp_scratch,
                                     double* env_scratch, double* precision, double* recall, void* stream) {
-    EP24_REQUIRE(npig && rec_thr && cls_range && precision && recall && num_classes > 0, EP24_E_ARG, "eval_accumulate: bad arguments");
+    EP24_REQUIRE(npig && rec_thr && precision && recall && num_classes > 0, EP24_E_ARG, "eval_accumulate: bad arguments");
     EP24_REQUIRE(n == 0 || (order && rec_cls && rec_tp && ctp_scratch && env_scratch), EP24_E_ARG, "eval_accumulate: null record buffer");
-    EP24_REQUIRE(hipMemsetAsync(cls_range, 0, sizeof(int64_t) * 2 * (size_t)num_classes, S_) == hipSuccess, EP24_E_LAUNCH,
-                 "eval_accumulate: memset failed");
-    if (n > 0) {
-        const long blocks = (n + 255) / 256;
-        hipLaunchKernelGGL(class_range_kernel, dim3((unsigned)(blocks > 4096 ? 4096 : blocks)), dim3(256), 0, S_, order, rec_cls, n,
-                           num_classes, cls_range);
-    }
-    hipLaunchKernelGGL(accumulate_kernel, dim3(num_classes), dim3(256), 0, S_, order, rec_tp, cls_range, npig, num_classes, rec_thr,
-                       ctp_scratch, env_scratch, precision, recall);
+    // one area range, one maxDets, no ignore bits, no position filter: rec_tp is the rec_m of accumulate.h
+    launch_accumulate(order, nullptr, rec_cls, rec_tp, n, npig, num_classes, 1, nullptr, 1, rec_thr, ctp_scratch, env_scratch, precision,
+                      recall, S_);
     EP24_LAUNCH_CHECK("ep24_eval_accumulate");
     return EP24_OK;
 }

@@ -16,7 +16,7 @@
 //   counts      ends -> run lengths: one thread per run takes the difference to the end before it; a mask's last run ends at H * W
 // Integer work only: no floating point, no atomics.  Every mask word is read once by count and once by emit (plus one or two words per
 // (mask, word column) for the row-0 carry).
-#include "common.h"
+#include "wave_scan.h"
 
 namespace {
 
@@ -129,12 +129,7 @@ __global__ __launch_bounds__(256) void rle_colscan_kernel(int32_t* colcnt, const
         for (int x0 = 0; x0 < m.W; x0 += 64) {
             const int x = x0 + lane;
             const int v = x < m.W ? c[x] : 0;
-            int inc = v;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const int u = __shfl_up(inc, o, 64);
-                if (lane >= o) inc += u;
-            }
+            const int inc = wave_incl_sum(v, lane);
             if (x < m.W) c[x] = carry + inc - v;
             carry += __shfl(inc, 63, 64);
         }
@@ -150,12 +145,7 @@ __global__ __launch_bounds__(1024) void rle_offsets_kernel(long long* offsets, l
     long long carry = 0;
     for (long i0 = 0; i0 < N; i0 += 1024) {
         const long i = i0 + tid;
-        long long inc = i < N ? offsets[1 + i] : 0;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const long long u = __shfl_up(inc, o, 64);
-            if (lane >= o) inc += u;
-        }
+        const long long inc = wave_incl_sum(i < N ? offsets[1 + i] : 0LL, lane);
         if (lane == 63) wsum[wv] = inc;
         __syncthreads();
         long long before = 0, all = 0;

@@ -9,17 +9,17 @@
 //   segm_match        one wave per (image, category) group: evaluateImg for every area range and IoU threshold.  Lanes own GTs
 //                     (g = lane, lane + 64, ...), detections are walked in the host's order; the first 64 GTs' state lives in
 //                     registers, GTs beyond them keep their matched bits in caller scratch (one int64 per GT)
-//   segm_accumulate   one workgroup per (class, area range, maxDets) over the records ep24_eval_sort ordered: cumulative TP / valid
-//                     counts, precision envelope from the right, the 101 recall look-ups, all in double
+//   segm_accumulate   the accumulate kernel of accumulate.h (shared with evaluate.hip): one workgroup per (class, area range,
+//                     maxDets) over the records ep24_eval_sort ordered: cumulative TP / valid counts, precision envelope from
+//                     the right, the 101 recall look-ups, all in double
 //
 // Determinism: the only atomics are the integer sums of non-ignored GTs per (class, area range).  Records are written at the
 // detection's own index, so nothing is appended.  No floating-point atomics.
-#include "common.h"
+#include "accumulate.h"
 
 namespace {
 
 constexpr int SE_T = 10;             // IoU thresholds
-constexpr int SE_R = 101;            // recall thresholds
 constexpr int SE_MAX_A = 4;          // area ranges: SE_MAX_A * SE_T matched bits fit one int64
 constexpr int SE_MAX_M = 4;          // maxDets values
 constexpr int SE_MAX_DETS = 128;     // detections per group: the rank takes 7 bits of the record key
@@ -244,128 +244,6 @@ __global__ __launch_bounds__(256) void segm_match_kernel(const long long* mgrp, 
     }
 }
 
-// ---------------------------------------------------------------------------------------------- accumulate
-__global__ __launch_bounds__(256) void segm_class_range_kernel(const int32_t* order, const int32_t* rec_cls, long long n,
-                                                               long long* range) {
-    for (long long j = (long long)blockIdx.x * 256 + threadIdx.x; j < n; j += (long long)gridDim.x * 256) {
-        const int c = rec_cls[order[j]];
-        if (j == 0 || rec_cls[order[j - 1]] != c) range[2 * c] = j;
-        if (j == n - 1 || rec_cls[order[j + 1]] != c) range[2 * c + 1] = j + 1;
-    }
-}
-
-// grid (K, NA * NM): pycocotools accumulate of class k for area range a and max_dets[m].  A record beyond max_dets[m], or ignored
-// at the threshold, stays in the list with neither a TP nor an FP: it repeats its predecessor's (recall, precision) point, which
-// neither the envelope nor the left search sees.
-__global__ __launch_bounds__(256) void segm_accumulate_kernel(const int32_t* order, const long long* rec_key, const int32_t* rec_m,
-                                                              const long long* range, const int32_t* npig, int K, int NA, int NM,
-                                                              const int32_t* max_dets, const double* rthr, long long n_all,
-                                                              int32_t* ctp_all, double* env_all, double* precision, double* recall) {
-    __shared__ long long wsl[4];
-    __shared__ double wsd[4];
-    __shared__ long long carry_l;
-    __shared__ double carry_d;
-    const int k = blockIdx.x, am = blockIdx.y, a = am / NM, m = am - a * NM;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const long long stride = (long long)K * NA * NM, col = ((long long)k * NA + a) * NM + m;
-    const int np = npig[k * NA + a];
-    if (np == 0) {                                            // no GT to find in this class and range: excluded (-1)
-        for (int i = tid; i < SE_T * SE_R; i += 256) precision[(long long)i * stride + col] = -1.0;
-        if (tid < SE_T) recall[(long long)tid * stride + col] = -1.0;
-        return;
-    }
-    const long long s = range[2 * k], n = range[2 * k + 1] - s;
-    int32_t* ctp = ctp_all + (long long)am * n_all;
-    double* env = env_all + (long long)am * n_all;
-    const int md = max_dets[m];
-    const double dnp = (double)np;
-    for (int t = 0; t < SE_T; ++t) {
-        // inclusive counts of TPs (low word) and of TPs + FPs (high word); pr_j = tp / (tp + fp + eps)
-        if (tid == 0) carry_l = 0;
-        __syncthreads();
-        for (long long b0 = 0; b0 < n; b0 += 1024) {
-            long long v[4], sum = 0;
-            for (int q = 0; q < 4; ++q) {
-                const long long jj = b0 + tid * 4 + q;
-                v[q] = 0;
-                if (jj < n) {
-                    const int rec = order[s + jj];
-                    const int mm = rec_m[(long long)rec * NA + a];
-                    const bool in = (int)(rec_key[rec] & 127) < md && !((mm >> (16 + t)) & 1);
-                    if (in) v[q] = (1LL << 32) | ((mm >> t) & 1);
-                }
-                sum += v[q];
-            }
-            long long incl = sum;
-            for (int o = 1; o < 64; o <<= 1) {
-                const long long x = __shfl_up(incl, o, 64);
-                if (lane >= o) incl += x;
-            }
-            if (lane == 63) wsl[w] = incl;
-            __syncthreads();
-            long long run = carry_l + incl - sum;
-            for (int q = 0; q < w; ++q) run += wsl[q];
-            for (int q = 0; q < 4; ++q) {
-                const long long jj = b0 + tid * 4 + q;
-                run += v[q];
-                if (jj < n) {
-                    const int tp = (int)(run & 0xFFFFFFFFLL);
-                    ctp[s + jj] = tp;
-                    env[s + jj] = (double)tp / ((double)(run >> 32) + 2.220446049250313e-16);
-                }
-            }
-            __syncthreads();
-            if (tid == 0) carry_l += wsl[0] + wsl[1] + wsl[2] + wsl[3];
-            __syncthreads();
-        }
-        // envelope: pr_j = max over i >= j (chunks from the right)
-        if (tid == 0) carry_d = 0.0;
-        __syncthreads();
-        const long long nch = (n + 1023) / 1024;
-        for (long long ch = nch - 1; ch >= 0; --ch) {
-            const long long b0 = ch * 1024;
-            double v[4];
-            double mx = 0.0;
-            for (int q = 3; q >= 0; --q) {
-                const long long jj = b0 + tid * 4 + q;
-                v[q] = jj < n ? env[s + jj] : 0.0;
-                mx = fmax(mx, v[q]);
-            }
-            double incl = mx;                                 // suffix max over this lane and the lanes above it
-            for (int o = 1; o < 64; o <<= 1) {
-                const double x = __shfl_down(incl, o, 64);
-                if (lane + o < 64) incl = fmax(incl, x);
-            }
-            if (lane == 0) wsd[w] = incl;
-            __syncthreads();
-            double run = carry_d;
-            for (int q = w + 1; q < 4; ++q) run = fmax(run, wsd[q]);
-            const double above = __shfl_down(incl, 1, 64);
-            if (lane < 63) run = fmax(run, above);
-            for (int q = 3; q >= 0; --q) {
-                const long long jj = b0 + tid * 4 + q;
-                run = fmax(run, v[q]);
-                if (jj < n) env[s + jj] = run;
-            }
-            __syncthreads();
-            if (tid == 0) carry_d = fmax(fmax(fmax(carry_d, wsd[0]), fmax(wsd[1], wsd[2])), wsd[3]);
-            __syncthreads();
-        }
-        // the 101 recall thresholds: precision at the first j with rc_j >= r (searchsorted 'left'), 0 past the end
-        if (tid < SE_R) {
-            const double rt = rthr[tid];
-            long long lo = 0, hi = n;
-            while (lo < hi) {
-                const long long mid = (lo + hi) >> 1;
-                if ((double)ctp[s + mid] / dnp >= rt) hi = mid; else lo = mid + 1;
-            }
-            precision[((long long)t * SE_R + tid) * stride + col] = lo < n ? env[s + lo] : 0.0;
-        }
-        if (tid == 0) recall[(long long)t * stride + col] = n ? (double)ctp[s + n - 1] / dnp : 0.0;
-        __syncthreads();
-    }
-}
-
 }  // namespace
 
 #define S_ (hipStream_t) stream
@@ -418,23 +296,15 @@ extern "C" int ep24_segm_accumulate(const int32_t* order, const int64_t* rec_key
                                     int64_t n, const int32_t* npig, int num_classes, int NA, const int32_t* max_dets, int NM,
                                     const double* rec_thr, int64_t* cls_range, int32_t* ctp_scratch, double* env_scratch,
                                     double* precision, double* recall, void* stream) {
-    EP24_REQUIRE(npig && max_dets && rec_thr && cls_range && precision && recall, EP24_E_ARG, "segm_accumulate: null pointer");
+    EP24_REQUIRE(npig && max_dets && rec_thr && precision && recall, EP24_E_ARG, "segm_accumulate: null pointer");
     EP24_REQUIRE(n == 0 || (order && rec_key && rec_cls && rec_m && ctp_scratch && env_scratch), EP24_E_ARG,
                  "segm_accumulate: null record buffer");
     EP24_REQUIRE(num_classes > 0 && num_classes <= 65535 && n >= 0 && n <= 0x7FFFFFFFLL, EP24_E_UNSUPPORTED,
                  "segm_accumulate: num_classes=%d n=%lld", num_classes, (long long)n);
     EP24_REQUIRE(NA >= 1 && NA <= SE_MAX_A && NM >= 1 && NM <= SE_MAX_M, EP24_E_UNSUPPORTED,
                  "segm_accumulate: %d area ranges, %d maxDets (1..%d, 1..%d)", NA, NM, SE_MAX_A, SE_MAX_M);
-    EP24_REQUIRE(hipMemsetAsync(cls_range, 0, sizeof(int64_t) * 2 * (size_t)num_classes, S_) == hipSuccess, EP24_E_LAUNCH,
-                 "segm_accumulate: memset failed");
-    if (n > 0) {
-        const long blocks = (long)((n + 255) / 256);
-        hipLaunchKernelGGL(segm_class_range_kernel, dim3((unsigned)(blocks > 4096 ? 4096 : blocks)), dim3(256), 0, S_, order, rec_cls,
-                           (long long)n, (long long*)cls_range);
-    }
-    hipLaunchKernelGGL(segm_accumulate_kernel, dim3(num_classes, NA * NM), dim3(256), 0, S_, order, (const long long*)rec_key, rec_m,
-                       (const long long*)cls_range, npig, num_classes, NA, NM, max_dets, rec_thr, (long long)n, ctp_scratch,
-                       env_scratch, precision, recall);
+    launch_accumulate(order, rec_key, rec_cls, rec_m, n, npig, num_classes, NA, max_dets, NM, rec_thr, ctp_scratch, env_scratch, precision,
+                      recall, S_);
     EP24_LAUNCH_CHECK("ep24_segm_accumulate");
     return EP24_OK;
 }

@@ -100,6 +100,24 @@ def _pow2(n):
     return P
 
 
+def sort_records(key, cls, low_bits, cls_bits):
+    """``ep24_eval_sort`` with its scratch: the int32 order of the records by (class, key), the passes covering the key's low
+    ``low_bits`` bits, its high half and the class's low ``cls_bits`` bits."""
+    n = key.numel()
+    if n > 0x7FFFFFFF:
+        raise Ep24Error("ep24: %d records: at most 2^31 - 1 (EP24_E_UNSUPPORTED)" % n)
+    dev = key.device
+    order = torch.empty(n, dtype=torch.int32, device=dev)
+    if n:
+        key_tmp = torch.empty(2 * n, dtype=torch.int64, device=dev)
+        cls_tmp = torch.empty(2 * n, dtype=torch.int32, device=dev)
+        idx_tmp = torch.empty(2 * n, dtype=torch.int32, device=dev)
+        hist = torch.empty(256 * ((n + 4095) // 4096), dtype=torch.int32, device=dev)
+        call("eval_sort", ptr(key), ptr(cls), n, low_bits, cls_bits, ptr(key_tmp), ptr(cls_tmp), ptr(idx_tmp), ptr(hist), ptr(order),
+             stream_ptr())
+    return order
+
+
 class Evaluator24:
     """``Evaluator24(num_classes, iou_type="circle24", max_dets=100, conf_thre=0.01, nms_thre=0.65, nms_iou="rect",
     max_candidates=None)``.  ``nms_iou`` / ``max_candidates`` are ``ep24.infer.postprocess``'s: ``"poly24"`` lets ``update``
@@ -251,19 +269,7 @@ class Evaluator24:
         else:
             key = torch.zeros(0, dtype=torch.int64, device=dev)
             cls = p = tp = torch.zeros(0, dtype=torch.int32, device=dev)
-        n = key.numel()
-        order = torch.empty(n, dtype=torch.int32, device=dev)
-        if n:
-            if n > 0x7FFFFFFF:
-                raise Ep24Error("ep24: %d records: at most 2^31 - 1 (EP24_E_UNSUPPORTED)" % n)
-            key_tmp = torch.empty(2 * n, dtype=torch.int64, device=dev)
-            cls_tmp = torch.empty(2 * n, dtype=torch.int32, device=dev)
-            idx_tmp = torch.empty(2 * n, dtype=torch.int32, device=dev)
-            hist = torch.empty(256 * ((n + 4095) // 4096), dtype=torch.int32, device=dev)
-            low_bits = 7 + max(self.seq - 1, 0).bit_length()
-            cls_bits = max(self.num_classes - 1, 0).bit_length()
-            call("eval_sort", ptr(key), ptr(cls), n, low_bits, cls_bits, ptr(key_tmp), ptr(cls_tmp), ptr(idx_tmp), ptr(hist), ptr(order),
-                 stream_ptr())
+        order = sort_records(key, cls, 7 + max(self.seq - 1, 0).bit_length(), max(self.num_classes - 1, 0).bit_length())
         return key, cls, p, tp, order
 
     def records(self):
@@ -288,10 +294,9 @@ class Evaluator24:
         n = key.numel()
         _, _, rthr = _device_consts(dev)
         out = torch.empty(10 * 101 * C + 10 * C, dtype=torch.float64, device=dev)
-        rng = torch.empty(2 * C, dtype=torch.int64, device=dev)
         ctp = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
         env = torch.empty(max(n, 1), dtype=torch.float64, device=dev)
-        call("eval_accumulate", ptr(order), ptr(cls), ptr(tp), n, ptr(self._npig), C, ptr(rthr), ptr(rng), ptr(ctp), ptr(env),
+        call("eval_accumulate", ptr(order), ptr(cls), ptr(tp), n, ptr(self._npig), C, ptr(rthr), None, ptr(ctp), ptr(env),
              ptr(out), ptr(out, 10 * 101 * C), stream_ptr())
         if int(self._err.item()):
             raise Ep24Error("ep24: eval_match met an image with more detections than its scratch holds")

@@ -27,9 +27,8 @@ import torch
 
 from . import _lib, cocomask
 from ._lib import Ep24Error, call, ptr, stream_ptr
+from .evaluate import IOU_THRS, REC_THRS, sort_records
 
-IOU_THRS = np.linspace(0.5, 0.95, 10)                    # float64, as pycocotools Params
-REC_THRS = np.linspace(0.0, 1.0, 101)
 AREA_RANGES = ((0 ** 2, 1e5 ** 2), (0 ** 2, 32 ** 2), (32 ** 2, 96 ** 2), (96 ** 2, 1e5 ** 2))
 AREA_LABELS = ("all", "small", "medium", "large")
 MAX_DETS_LIMIT = 128                                     # the position in the group takes 7 bits of the record key
@@ -315,23 +314,13 @@ class SegmEvaluator:
         self.chunks = len(chunks)
         for j0, j1 in chunks:
             self._chunk(plan, j0, j1, dev, thr, rng, rec, npig)
-        order = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
-        s = stream_ptr()
-        if n:
-            key_tmp = torch.empty(2 * n, dtype=torch.int64, device=dev)
-            cls_tmp = torch.empty(2 * n, dtype=torch.int32, device=dev)
-            idx_tmp = torch.empty(2 * n, dtype=torch.int32, device=dev)
-            hist = torch.empty(256 * ((n + 4095) // 4096), dtype=torch.int32, device=dev)
-            low_bits = 7 + max(len(self.gt["img_ids"]) - 1, 0).bit_length()
-            call("eval_sort", ptr(rec["key"]), ptr(rec["cls"]), n, low_bits, max(K - 1, 0).bit_length(), ptr(key_tmp), ptr(cls_tmp),
-                 ptr(idx_tmp), ptr(hist), ptr(order), s)
+        order = sort_records(rec["key"][:n], rec["cls"][:n], 7 + max(len(self.gt["img_ids"]) - 1, 0).bit_length(), max(K - 1, 0).bit_length())
         np_, nr_ = 10 * 101 * K * NA * NM, 10 * K * NA * NM
         out = torch.empty(np_ + nr_, dtype=torch.float64, device=dev)
-        cls_range = torch.empty(2 * K, dtype=torch.int64, device=dev)
         ctp = torch.empty(NA * NM * max(n, 1), dtype=torch.int32, device=dev)
         env = torch.empty(NA * NM * max(n, 1), dtype=torch.float64, device=dev)
         call("segm_accumulate", ptr(order), ptr(rec["key"]), ptr(rec["cls"]), ptr(rec["m"]), n, ptr(npig), K, NA, ptr(md), NM, ptr(rthr),
-             ptr(cls_range), ptr(ctp), ptr(env), ptr(out), ptr(out, np_), s)
+             None, ptr(ctp), ptr(env), ptr(out), ptr(out, np_), stream_ptr())
         host = out.cpu().numpy()                                                     # the one device-to-host copy
         precision, recall = host[:np_].reshape(10, 101, K, NA, NM), host[np_:].reshape(10, K, NA, NM)
         stats, lines = summarize_tables(precision, recall, self.max_dets, self.area_labels)

@@ -649,8 +649,10 @@ int ep24_eval_match(const float* labels, int L, int B, const float* rows, int nc
 int ep24_eval_sort(const int64_t* key, const int32_t* cls, int64_t n, int key_low_bits, int cls_bits, int64_t* key_tmp,
                    int32_t* cls_tmp, int32_t* idx_tmp, int32_t* hist, int32_t* order, void* stream);
 /* One workgroup per class over the sorted records: precision[10][101][num_classes] and recall[10][num_classes] (double) as
- * pycocotools accumulate computes them, -1 for a class without GTs.  rec_thr[101] double; cls_range [num_classes][2] int64,
- * ctp_scratch [n] int32, env_scratch [n] double. */
+ * pycocotools accumulate computes them, -1 for a class without GTs.  The kernel is ep24_segm_accumulate's (E6) with one area
+ * range, one maxDets, no ignore bits and no position filter; each workgroup finds its class's records in the sorted order by
+ * binary search.  rec_thr[101] double; ctp_scratch [n] int32, env_scratch [n] double.  cls_range: unused since the two accumulate
+ * kernels became one; may be null; neither read nor written. */
 int ep24_eval_accumulate(const int32_t* order, const int32_t* rec_cls, const int32_t* rec_tp, int64_t n, const int32_t* npig,
                          int num_classes, const double* rec_thr, int64_t* cls_range, int32_t* ctp_scratch,
                          double* env_scratch, double* precision, double* recall, void* stream);
@@ -865,8 +867,10 @@ int ep24_rle_counts(const int32_t* ends, const int64_t* offsets, const int64_t* 
  * ep24_segm_accumulate: over the n records in the order ep24_eval_sort gave, for every class k, area range a and max_dets[m] (int32
  *   [NM], NM <= 4): only records whose position is < max_dets[m] count, a record ignored at t is neither TP nor FP at t;
  *   precision[10][101][K][NA][NM] and recall[10][K][NA][NM] double with the expressions of ep24_eval_accumulate - tp / (fp + tp + eps),
- *   the envelope from the right, the left search over recall = tp / npig - and -1 where npig[k][a] == 0.  rec_thr[101] double;
- *   cls_range [K][2] int64, ctp_scratch [NA * NM][n] int32, env_scratch [NA * NM][n] double.  K <= 65535.
+ *   the envelope from the right, the left search over recall = tp / npig - and -1 where npig[k][a] == 0.  One kernel serves both entry points
+ *   (csrc/accumulate.h); the records being ordered by class, each workgroup finds its class's range by binary search.  rec_thr[101]
+ *   double; ctp_scratch [NA * NM][n] int32, env_scratch [NA * NM][n] double.  K <= 65535.  cls_range: unused since the two accumulate
+ *   kernels became one; may be null; neither read nor written.
  * ------------------------------------------------------------------------------------------------ */
 int ep24_segm_mask_stats(const uint32_t* bits, const int64_t* tab, int N, int32_t* bbox, int32_t* area, void* stream);
 int ep24_segm_iou(const uint32_t* bits, const int64_t* tab, int N, const int32_t* bbox, const int32_t* area,

@@ -164,6 +164,43 @@ def test_update_equals_update_detections_of_postprocess():
         assert np.array_equal(sa["precision"], sb["precision"]) and np.array_equal(sa["recall"], sb["recall"])
 
 
+def test_eval_accumulate_across_chunk_boundaries():
+    """The synthetic records of tests/test_gpu_segmeval.py (classes of 2 500, 1 024 and 1 025 records: sums and maxima carried over
+    the accumulate kernel's chunks of 1 024) in the 24-point shape - the TP bits of range 0, npig [K]: ep24_eval_accumulate bit-equal
+    to the segm oracle at one maxDets that keeps every record and to ep24_segm_accumulate on the same buffers with NA = NM = 1."""
+    import segmeval_oracle as ora
+    from ep24._lib import call, ptr, stream_ptr
+    from test_gpu_segmeval import CHUNK_K as K, chunk_records, dev, framed, frames_intact
+    rec, _ = chunk_records()
+    rec = dict(rec, m=rec["m"][:, :1] & 0x3FF, npig=rec["npig"][:, :1])
+    want_p, want_r = (x[..., 0, 0] for x in ora.accumulate(rec, K, (128,)))
+    n = len(rec["cls"])
+    ranks = ora.score_ranks(rec["score"]).astype(np.uint64)
+    key = dev(((ranks << np.uint64(32)) | (rec["seq"].astype(np.uint64) << np.uint64(7)) | rec["rank"].astype(np.uint64)).view(np.int64))
+    cls, tp, npig = dev(rec["cls"].astype(np.int32)), dev(rec["m"].astype(np.int32).reshape(-1)), dev(rec["npig"].astype(np.int32).reshape(-1))
+    order = E.sort_records(key, cls, 7 + int(rec["seq"].max()).bit_length(), max(K - 1, 1).bit_length())
+    md, rthr = dev(np.array([128], dtype=np.int32)), dev(ora.REC_THRS.copy())
+    npr, nrc = 10 * 101 * K, 10 * K
+    got = []
+    for segm in (False, True):
+        p_big, prec, f64 = framed(npr, torch.float64)
+        r_big, recl, _ = framed(nrc, torch.float64)
+        ctp = torch.full((n,), -1, dtype=torch.int32, device=DEV)
+        env = torch.full((n,), float("nan"), dtype=torch.float64, device=DEV)
+        if segm:
+            call("segm_accumulate", ptr(order), ptr(key), ptr(cls), ptr(tp), n, ptr(npig), K, 1, ptr(md), 1, ptr(rthr), None, ptr(ctp),
+                 ptr(env), ptr(prec), ptr(recl), stream_ptr())
+        else:
+            call("eval_accumulate", ptr(order), ptr(cls), ptr(tp), n, ptr(npig), K, ptr(rthr), None, ptr(ctp), ptr(env), ptr(prec),
+                 ptr(recl), stream_ptr())
+        assert frames_intact(p_big, npr, f64) and frames_intact(r_big, nrc, f64)
+        got.append((prec.cpu().numpy().reshape(10, 101, K), recl.cpu().numpy().reshape(10, K)))
+    for got_p, got_r in got:
+        assert np.array_equal(got_p.view(np.int64), want_p.view(np.int64))
+        assert np.array_equal(got_r.view(np.int64), want_r.view(np.int64))
+    assert ((want_p > 0) & (want_p < 0.99)).any() and np.all(want_p[:, :, 4] == -1) and np.all(want_p[:, :, 3] == 0)
+
+
 def _small_exp():
     sys.path.insert(0, Y24)
     from exp import get_exp

@@ -1,7 +1,7 @@
 """The ep24_segm_* kernels and ep24.segmeval.SegmEvaluator on the GPU against tests/segmeval_oracle.py, everything exact:
 mask statistics and crowd-aware IoU on random bit masks of mixed sizes inside sentinel frames, the matcher on the recorded
-scene's IoU blocks (whole and split over two calls) and on groups of more than 64 GTs, the accumulator on the oracle's records,
-the evaluator end to end on a dataset built here (three chunk sizes, three input forms) and eval_segm.py in a child process."""
+scene's IoU blocks (whole and split over two calls) and on groups of more than 64 GTs, the accumulator on the oracle's records
+and on classes longer than its chunk of 1 024 records, the evaluator end to end on a dataset built here (three chunk sizes, three input forms) and eval_segm.py in a child process."""
 import functools
 import json
 import os
@@ -230,17 +230,14 @@ def test_match_with_more_than_64_gts_and_ties():
 # ------------------------------------------------------------------------------------------------- the accumulator
 def run_accumulate(rec, K, max_dets):
     from ep24._lib import call, ptr, stream_ptr
+    from ep24.evaluate import sort_records
     n, NA, NM = len(rec["cls"]), rec["m"].shape[1], len(max_dets)
     ranks = ora.score_ranks(rec["score"]).astype(np.uint64)
     key = dev(((ranks << np.uint64(32)) | (rec["seq"].astype(np.uint64) << np.uint64(7)) | rec["rank"].astype(np.uint64)).view(np.int64))
     cls, m = dev(rec["cls"].astype(np.int32)), dev(rec["m"].astype(np.int32))
     npig = dev(rec["npig"].astype(np.int32))
     s = stream_ptr()
-    order = torch.empty(n, dtype=torch.int32, device=DEV)
-    key_tmp, cls_tmp = torch.empty(2 * n, dtype=torch.int64, device=DEV), torch.empty(2 * n, dtype=torch.int32, device=DEV)
-    idx_tmp, hist = torch.empty(2 * n, dtype=torch.int32, device=DEV), torch.empty(256 * ((n + 4095) // 4096), dtype=torch.int32, device=DEV)
-    call("eval_sort", ptr(key), ptr(cls), n, 7 + int(rec["seq"].max()).bit_length(), max(K - 1, 1).bit_length(), ptr(key_tmp), ptr(cls_tmp),
-         ptr(idx_tmp), ptr(hist), ptr(order), s)
+    order = sort_records(key, cls, 7 + int(rec["seq"].max()).bit_length(), max(K - 1, 1).bit_length())
     npr, nrc = 10 * 101 * K * NA * NM, 10 * K * NA * NM
     p_big, prec, f64 = framed(npr, torch.float64)
     r_big, recl, _ = framed(nrc, torch.float64)
@@ -270,6 +267,44 @@ def test_accumulate_on_the_oracle_records():
     want_p, want_r = ora.accumulate(rec, 4, (3, 128))
     got_p, got_r = run_accumulate(rec, 4, [3, 128])
     assert np.array_equal(got_p.view(np.int64), want_p.view(np.int64)) and np.array_equal(got_r.view(np.int64), want_r.view(np.int64))
+
+
+CHUNK_K, CHUNK_MAX_DETS = 5, (3, 100, 128)
+
+
+@functools.lru_cache(maxsize=None)
+def chunk_records():
+    """Synthetic records (no masks, no matcher) whose classes straddle the accumulate kernel's chunk of 1 024 records: class 0 two
+    full chunks and a tail of 452, class 1 exactly one chunk, class 2 one chunk and a tail of one, class 3 GTs and no record, class 4
+    records and no GT.  Two area ranges, ranks up to 124, scores on a grid of 0.01 (many ties), random TP bits and sparse ignore
+    bits disjoint from them; the records stand in a random order.  -> (records, the oracle's tables at CHUNK_MAX_DETS); shared, not
+    to be modified."""
+    rng = np.random.RandomState(23)
+    counts = (2500, 1024, 1025, 0, 37)
+    cls = np.concatenate([np.full(c, k, dtype=np.int64) for k, c in enumerate(counts)])
+    i = np.concatenate([np.arange(c, dtype=np.int64) for c in counts])
+    n = len(cls)
+    tp = rng.randint(0, 1024, size=(n, 2))
+    ig = np.zeros((n, 2), dtype=np.int64)
+    for t in range(10):
+        ig |= (rng.rand(n, 2) < 0.1).astype(np.int64) << t
+    ig &= ~tp
+    o = rng.permutation(n)
+    rec = {"cls": cls[o], "score": np.round(rng.rand(n), 2)[o], "seq": (i // 125)[o], "rank": (i % 125)[o],
+           "m": (tp | (ig << 16)).astype(np.int32)[o], "npig": np.array([[2507, 2500], [1024, 1030], [1025, 1026], [5, 3], [0, 0]], dtype=np.int64)}
+    return rec, ora.accumulate(rec, CHUNK_K, CHUNK_MAX_DETS)
+
+
+def test_accumulate_across_chunk_boundaries():
+    """Classes of 2 500, 1 024 and 1 025 records: the running sums and the running maximum cross from one chunk of 1 024 to the next."""
+    rec, (want_p, want_r) = chunk_records()
+    assert np.bincount(rec["cls"], minlength=CHUNK_K).tolist() == [2500, 1024, 1025, 0, 37] and rec["rank"].max() == 124
+    assert (rec["m"] >> 16).any() and not ((rec["m"] >> 16) & rec["m"] & 0x3FF).any()
+    got_p, got_r = run_accumulate(rec, CHUNK_K, list(CHUNK_MAX_DETS))
+    assert np.array_equal(got_p.view(np.int64), want_p.view(np.int64))
+    assert np.array_equal(got_r.view(np.int64), want_r.view(np.int64))
+    assert np.all(got_p[:, :, 3] == 0) and np.all(got_r[:, 3] == 0) and np.all(got_p[:, :, 4] == -1) and np.all(got_r[:, 4] == -1)
+    assert ((got_p > 0) & (got_p < 0.99)).any()
 
 
 # ------------------------------------------------------------------------------------------------- end to end

@@ -41,6 +41,7 @@ def main():
     A = pred.shape[1]
 
     def match():
+        ms.count.zero_()                                  # as Evaluator24._match: records are appended at *rec_count, the buffers hold one batch's
         call("eval_match", ptr(labels), labels.shape[1], B, ptr(pred), pred.shape[2], ptr(row_off), ptr(ws.keep), A, ptr(ws.count),
              ptr(ws.conf), ptr(ws.cls), C, ev._t, ptr(cs), ptr(thr), ev.max_dets, 0, ptr(ms.sort), E._pow2(A), ptr(ms.key), ptr(ms.cls),
              ptr(ms.p), ptr(ms.tp), ptr(ms.count), ptr(ev._npig), ptr(ev._err), stream_ptr())

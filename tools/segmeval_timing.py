@@ -3,7 +3,7 @@
     rocprofv3 --kernel-trace --stats --output-format csv -d OUT -o kt -- python tools/segmeval_timing.py [--reps 5]
 
 in a run of its own (no counters, no other tracing beside it).  The kernel times come from the trace's statistics
-(``segm_mask_stats_kernel``, ``segm_iou_kernel``, ``segm_match_kernel``, ``segm_accumulate_kernel``, beside ``rle_pack_bytes_kernel``,
+(``segm_mask_stats_kernel``, ``segm_iou_kernel``, ``segm_match_kernel``, ``accumulate_kernel``, beside ``rle_pack_bytes_kernel``,
 the cocomask decode kernels and the radix sort of ``ep24_eval_sort``).  The JSON line this prints carries the workload's sizes,
 the 12 numbers and the GPU-event time of whole ``evaluate()`` calls for orientation (host planning and JSON parsing included).
 
