@@ -5,6 +5,9 @@
 // area), so  |A and B| = sigma_A sigma_B * sum_e sum_f s_e s_f * integral over the common x range of min(h_e, h_f).
 // No inside tests, no sorting, continuous in the vertices: coincident edges, shared vertices and identical polygons are ordinary
 // cases.  Everything is double; the library is built with -ffp-contract=off, so every product and sum rounds on its own.
+//
+// The computation comes in three pieces (poly24_prepare, poly24_edge_accumulate, poly24_finish) that poly24_inter runs in a row on
+// one lane.  ep24_paste_labels (csrc/paste.hip) spreads the middle piece over 24 lanes, one edge of `a` each.
 #pragma once
 #include "common.h"
 
@@ -23,9 +26,12 @@ __device__ __forceinline__ double poly24_height(double x, double xa, double ha, 
     return ha + ((x - xa) * (hb - ha)) / (xb - xa);
 }
 
-// a, b: 24 vertices each as (x, y) pairs of fp32, promoted here.  Any NaN coordinate gives NaN (it never matches); vertex
-// boxes that do not overlap with positive width and height give exactly 0.0.
-__device__ inline double poly24_iou(const float* a, const float* b) {
+// What poly24_prepare found: a NaN coordinate, vertex boxes that do not overlap with positive width and height, or a pair to intersect
+enum { POLY24_NAN = 0, POLY24_APART = 1, POLY24_MEET = 2 };
+
+// a, b: 24 vertices each as (x, y) pairs of fp32, promoted here.  For a pair to intersect: *yb = the baseline of the heights and
+// *sa, *sb = the signed shoelace areas of a and b.
+__device__ __forceinline__ int poly24_prepare(const float* a, const float* b, double* yb_out, double* sa_out, double* sb_out) {
     double axl = INFINITY, axh = -INFINITY, ayl = INFINITY, ayh = -INFINITY;
     double bxl = INFINITY, bxh = -INFINITY, byl = INFINITY, byh = -INFINITY;
     bool nan = false;
@@ -35,8 +41,8 @@ __device__ inline double poly24_iou(const float* a, const float* b) {
         axl = fmin(axl, ax); axh = fmax(axh, ax); ayl = fmin(ayl, ay); ayh = fmax(ayh, ay);
         bxl = fmin(bxl, bx); bxh = fmax(bxh, bx); byl = fmin(byl, by); byh = fmax(byh, by);
     }
-    if (nan) return __builtin_nan("");
-    if (!(fmin(axh, bxh) - fmax(axl, bxl) > 0.0 && fmin(ayh, byh) - fmax(ayl, byl) > 0.0)) return 0.0;
+    if (nan) return POLY24_NAN;
+    if (!(fmin(axh, bxh) - fmax(axl, bxl) > 0.0 && fmin(ayh, byh) - fmax(ayl, byl) > 0.0)) return POLY24_APART;
     // the shoelace areas and the heights are taken relative to (xb, yb), the low corner of the joint box: a translation, exact in
     // real arithmetic, that keeps the rounding relative to the objects' size and not to their position in the image
     const double xb = fmin(axl, bxl), yb = fmin(ayl, byl);
@@ -52,42 +58,76 @@ __device__ inline double poly24_iou(const float* a, const float* b) {
     }
     sa *= 0.5;
     sb *= 0.5;
-    double S = 0.0;
-    for (int i = 0; i < 24; ++i) {
-        const int i1 = i == 23 ? 0 : i + 1;
-        const double ex0 = a[2 * i], ex1 = a[2 * i1];
-        if (ex0 == ex1) continue;
-        const double eh0 = (double)a[2 * i + 1] - yb, eh1 = (double)a[2 * i1 + 1] - yb;
-        const bool er = ex1 > ex0;                            // left to right as stored
-        const double exa = er ? ex0 : ex1, eha = er ? eh0 : eh1, exb = er ? ex1 : ex0, ehb = er ? eh1 : eh0;
-        for (int j = 0; j < 24; ++j) {
-            const int j1 = j == 23 ? 0 : j + 1;
-            const double fx0 = b[2 * j], fx1 = b[2 * j1];
-            if (fx0 == fx1) continue;
-            const double fh0 = (double)b[2 * j + 1] - yb, fh1 = (double)b[2 * j1 + 1] - yb;
-            const bool fr = fx1 > fx0;
-            const double fxa = fr ? fx0 : fx1, fha = fr ? fh0 : fh1, fxb = fr ? fx1 : fx0, fhb = fr ? fh1 : fh0;
-            const double xl = fmax(exa, fxa), xr = fmin(exb, fxb);
-            if (!(xl < xr)) continue;
-            const double al = poly24_height(xl, exa, eha, exb, ehb), ar = poly24_height(xr, exa, eha, exb, ehb);
-            const double bl = poly24_height(xl, fxa, fha, fxb, fhb), br = poly24_height(xr, fxa, fha, fxb, fhb);
-            const double dl = al - bl, dr = ar - br;
-            const double ml = fmin(al, bl), mr = fmin(ar, br);
-            double term;
-            if ((dl < 0.0 && dr > 0.0) || (dl > 0.0 && dr < 0.0)) {
-                // the edges cross inside the range: two trapezoids under min(e, f) that meet at the crossing height
-                const double t = dl / (dl - dr);
-                const double xm = xl + t * (xr - xl), hm = al + t * (ar - al);
-                term = 0.5 * (ml + hm) * (xm - xl) + 0.5 * (hm + mr) * (xr - xm);
-            } else {
-                term = 0.5 * (ml + mr) * (xr - xl);
-            }
-            S += (er == fr) ? term : -term;
+    *yb_out = yb;
+    *sa_out = sa;
+    *sb_out = sb;
+    return POLY24_MEET;
+}
+
+// S += the signed terms of edge i of a against the 24 edges of b, in the order of b's edges
+__device__ __forceinline__ void poly24_edge_accumulate(const float* a, const float* b, int i, double yb, double& S) {
+    const int i1 = i == 23 ? 0 : i + 1;
+    const double ex0 = a[2 * i], ex1 = a[2 * i1];
+    if (ex0 == ex1) return;
+    const double eh0 = (double)a[2 * i + 1] - yb, eh1 = (double)a[2 * i1 + 1] - yb;
+    const bool er = ex1 > ex0;                            // left to right as stored
+    const double exa = er ? ex0 : ex1, eha = er ? eh0 : eh1, exb = er ? ex1 : ex0, ehb = er ? eh1 : eh0;
+    for (int j = 0; j < 24; ++j) {
+        const int j1 = j == 23 ? 0 : j + 1;
+        const double fx0 = b[2 * j], fx1 = b[2 * j1];
+        if (fx0 == fx1) continue;
+        const double fh0 = (double)b[2 * j + 1] - yb, fh1 = (double)b[2 * j1 + 1] - yb;
+        const bool fr = fx1 > fx0;
+        const double fxa = fr ? fx0 : fx1, fha = fr ? fh0 : fh1, fxb = fr ? fx1 : fx0, fhb = fr ? fh1 : fh0;
+        const double xl = fmax(exa, fxa), xr = fmin(exb, fxb);
+        if (!(xl < xr)) continue;
+        const double al = poly24_height(xl, exa, eha, exb, ehb), ar = poly24_height(xr, exa, eha, exb, ehb);
+        const double bl = poly24_height(xl, fxa, fha, fxb, fhb), br = poly24_height(xr, fxa, fha, fxb, fhb);
+        const double dl = al - bl, dr = ar - br;
+        const double ml = fmin(al, bl), mr = fmin(ar, br);
+        double term;
+        if ((dl < 0.0 && dr > 0.0) || (dl > 0.0 && dr < 0.0)) {
+            // the edges cross inside the range: two trapezoids under min(e, f) that meet at the crossing height
+            const double t = dl / (dl - dr);
+            const double xm = xl + t * (xr - xl), hm = al + t * (ar - al);
+            term = 0.5 * (ml + hm) * (xm - xl) + 0.5 * (hm + mr) * (xr - xm);
+        } else {
+            term = 0.5 * (ml + mr) * (xr - xl);
         }
+        S += (er == fr) ? term : -term;
     }
+}
+
+// the intersection area from the sum S of all terms and the signed areas; *aa, *ab = the absolute areas
+__device__ __forceinline__ double poly24_finish(double S, double sa, double sb, double* aa_out, double* ab_out) {
     const double aa = fabs(sa), ab = fabs(sb);
     const double sg = ((sa < 0.0) != (sb < 0.0)) ? -S : S;
-    const double inter = fmin(fmax(sg, 0.0), fmin(aa, ab));
+    *aa_out = aa;
+    *ab_out = ab;
+    return fmin(fmax(sg, 0.0), fmin(aa, ab));
+}
+
+// The intersection area of two 24-gons and their absolute shoelace areas (*aa of a, *ab of b).  Any NaN coordinate: NaN and NaN
+// areas.  Vertex boxes that do not overlap with positive width and height: exactly 0.0, and the areas, which are then not needed,
+// are left at 0.0.
+__device__ inline double poly24_inter(const float* a, const float* b, double* aa_out, double* ab_out) {
+    double yb, sa, sb;
+    const int kind = poly24_prepare(a, b, &yb, &sa, &sb);
+    if (kind != POLY24_MEET) {
+        *aa_out = *ab_out = kind == POLY24_NAN ? __builtin_nan("") : 0.0;
+        return *aa_out;
+    }
+    double S = 0.0;
+    for (int i = 0; i < 24; ++i) poly24_edge_accumulate(a, b, i, yb, S);
+    return poly24_finish(S, sa, sb, aa_out, ab_out);
+}
+
+// Area IoU.  Any NaN coordinate gives NaN (it never matches); vertex boxes that do not overlap with positive width and height
+// give exactly 0.0.
+__device__ inline double poly24_iou(const float* a, const float* b) {
+    double aa, ab;
+    const double inter = poly24_inter(a, b, &aa, &ab);
+    if (inter != inter) return inter;                         // a NaN coordinate (fmin / fmax in poly24_finish never return one)
     const double uni = aa + ab - inter;
     return uni > 0.0 ? inter / uni : 0.0;
 }

@@ -14,6 +14,11 @@ Mixup blends one more source of the batch into a mosaic image, in the same two l
 averaged with the mosaic as ``(a + b) >> 1`` BEFORE HSV; its polygons go through their own map and the same keep and re-cast
 rules, behind the four tiles' rows.
 
+Copy-paste (``sample_paste``, ``paste_batch``; csrc/paste.hip) is a post-pass of two more launches over the finished batch: an image
+pastes objects of another image of the batch through a rigid integer transform (shift, optional mirror), each object's 24-gon being
+its mask, wherever the object lies inside the image and hides less than ``paste_ioa`` of every object already there.  It is
+YOLOv5's ``copy_paste``, which stock YOLOX and the reference lack; off unless ``AugParams.paste`` is set.
+
 Deviations from the reference, on purpose: the three mosaic partners and the mixup partner of an image come from the SAME BATCH
 (the reference draws them from the whole dataset; here nothing extra is uploaded); the reference mixes only when the mosaic has
 labels left (``len(mosaic_labels) != 0``), which only the GPU knows - here the host-known stand-in is "the four tiles' sources
@@ -61,7 +66,10 @@ class AugParams:
     letterboxed at the top left of an S canvas, and ``M`` is whatever the caller sets (``sample_params``: identity).
     Mixup, off by default (``sample_mixup`` fills it): ``mixup`` bool [n]; ``mix_partner`` int [n] = source index of the blended
     image; ``mix_jit`` float64 [n] = scale of its letterbox canvas; ``mix_flip`` bool [n]; ``mix_off`` int [n,2] = (x_off, y_off),
-    the corner of the S_h x S_w window cut out of the jittered canvas."""
+    the corner of the S_h x S_w window cut out of the jittered canvas.
+    Copy-paste, off by default (``sample_paste`` fills it): ``paste`` bool [n]; ``paste_partner`` int [n] = the image of the batch
+    whose objects are pasted (the image itself is allowed); ``paste_flip`` bool [n]; ``paste_off`` int [n,2] = (dx, dy) in output
+    pixels; ``paste_select`` uint64 [n], bit k = the partner's k-th surviving row may be pasted."""
 
     def __init__(self, n):
         self.n = n
@@ -78,6 +86,11 @@ class AugParams:
         self.mix_jit = np.ones(n, dtype=np.float64)
         self.mix_flip = np.zeros(n, dtype=bool)
         self.mix_off = np.zeros((n, 2), dtype=np.int64)
+        self.paste = np.zeros(n, dtype=bool)
+        self.paste_partner = np.arange(n, dtype=np.int64)
+        self.paste_flip = np.zeros(n, dtype=bool)
+        self.paste_off = np.zeros((n, 2), dtype=np.int64)
+        self.paste_select = np.zeros(n, dtype=np.uint64)
 
     def set_matrix(self, i, M):
         self.M[i] = np.asarray(M, dtype=np.float64).reshape(2, 3)
@@ -212,6 +225,111 @@ def mixup_layout(params, i, sizes, input_size):
     return ints, dbl
 
 
+def paste_rng(seed, epoch, it):
+    """The generator of the copy-paste draws of batch (epoch, it): its own stream, so ``sample_params``' and ``sample_mixup``'s
+    draws do not move."""
+    return np.random.RandomState(np.array([seed, epoch, it, 2], dtype=np.uint32))
+
+
+def sample_paste(rng, params, n, input_size, paste_prob, obj_prob=0.5):
+    """Fills the copy-paste fields of ``params`` (an ``AugParams`` for ``n`` images) from ``rng`` (``paste_rng``) and returns
+    ``params``.
+
+    Per output image, in this order and ALWAYS all 69 numbers, whatever the outcome:
+      1  u_on    = random_sample()              paste if u_on < paste_prob
+      2  partner = randint(0, n)                the image of the batch whose objects are pasted (the image itself is allowed)
+      3  u_flip  = random_sample()              flip if u_flip < 0.5
+      4  dx      = randint(-(S_w // 2), S_w // 2 + 1)      i.e. [-S_w//2, S_w//2], in output pixels
+      5  dy      = randint(-(S_h // 2), S_h // 2 + 1)
+      6-69 u_k   = random_sample(), k = 0 .. 63            bit k of the select mask is set if u_k < obj_prob
+    Which of the selected objects are pasted is decided on the GPU (``ep24_paste_labels``: inside the image, and hiding less than
+    the IoA threshold of every object already there)."""
+    if params.n != n:
+        raise ValueError("sample_paste: %d images, parameters for %d" % (n, params.n))
+    S_h, S_w = int(input_size[0]), int(input_size[1])
+    for i in range(n):
+        u_on = rng.random_sample()
+        partner = int(rng.randint(0, n))
+        u_flip = rng.random_sample()
+        dx = int(rng.randint(-(S_w // 2), S_w // 2 + 1))
+        dy = int(rng.randint(-(S_h // 2), S_h // 2 + 1))
+        bits = rng.random_sample(64) < obj_prob
+        params.paste[i] = u_on < paste_prob
+        params.paste_partner[i], params.paste_flip[i], params.paste_off[i] = partner, u_flip < 0.5, (dx, dy)
+        params.paste_select[i] = np.uint64(sum(1 << k for k in range(64) if bits[k]))
+    return params
+
+
+def paste_descriptors(params):
+    """The copy-paste descriptors of a batch as the kernels take them (include/ep24.h): int64 [n, 8] = (on, partner, flip, dx, dy,
+    select, 0, 0).  The library cannot read a descriptor in device memory, so this is the check that refuses a partner outside the
+    batch (``EP24_E_ARG``); the kernels treat such a descriptor as off."""
+    n = params.n
+    desc = np.zeros((n, 8), dtype=np.int64)
+    desc[:, 0] = np.asarray(params.paste, dtype=bool)
+    desc[:, 1] = params.paste_partner
+    desc[:, 2] = np.asarray(params.paste_flip, dtype=bool)
+    desc[:, 3:5] = params.paste_off
+    desc[:, 5] = np.asarray(params.paste_select, dtype=np.uint64).view(np.int64)
+    check_paste_descriptors(desc)
+    return desc
+
+
+def check_paste_descriptors(desc):
+    desc = np.asarray(desc)
+    n = len(desc)
+    bad = (desc[:, 0] != 0) & ((desc[:, 1] < 0) | (desc[:, 1] >= n))
+    if bad.any():
+        i = int(np.nonzero(bad)[0][0])
+        raise _lib.Ep24Error("ep24_paste_labels failed (-1, EP24_E_ARG): copy-paste partner %d of image %d is not in the batch of %d"
+                             % (int(desc[i, 1]), i, n))
+
+
+def paste_batch(pre_images, pre_labels, pre_counts, desc, min_margin=2.0, ioa_thr=0.30, out_images=None, out_labels=None,
+                counts=None, check=True):
+    """The copy-paste post-pass (``ep24_paste_labels``, then ``ep24_paste_u8`` on its rows) over a batch that the augmentation's two
+    launches produced: pre_images [n,3,S_h,S_w] fp32, pre_labels [n,max_labels,51] fp32, pre_counts [n] int32, ``desc`` int64
+    [n,8] (``paste_descriptors``).  The inputs are a snapshot: the outputs are other buffers.
+    Returns (images, labels, counts [n] int32, paste_range [n,2] int32)."""
+    _lib.require_gpu()
+    n, _, S_h, S_w = (int(v) for v in pre_images.shape)
+    max_labels = int(pre_labels.shape[1])
+    dev = pre_images.device
+    if not (pre_images.dtype == pre_labels.dtype == torch.float32 and pre_counts.dtype == torch.int32 and pre_images.is_contiguous()
+            and pre_labels.is_contiguous() and pre_counts.is_contiguous() and tuple(pre_labels.shape) == (n, max_labels, 51)
+            and tuple(pre_counts.shape) == (n,)):
+        raise ValueError("paste_batch takes contiguous fp32 [n,3,S_h,S_w] images, fp32 [n,max_labels,51] labels and int32 [n] counts")
+    desc = np.array(desc, dtype=np.int64).reshape(n, 8)                            # a copy: the upload wants a writable array
+    if check:
+        check_paste_descriptors(desc)
+    if out_images is None:
+        out_images = torch.empty_like(pre_images)
+    if out_labels is None:
+        out_labels = torch.empty_like(pre_labels)
+    if counts is None:
+        counts = torch.empty(n, dtype=torch.int32, device=dev)
+    ranges = torch.empty(n, 2, dtype=torch.int32, device=dev)
+    desc_t = torch.from_numpy(desc).to(dev)
+    call("paste_labels", ptr(pre_labels), ptr(pre_counts), ptr(desc_t), n, S_h, S_w, float(min_margin), float(ioa_thr),
+         ptr(out_labels), ptr(counts), ptr(ranges), max_labels, stream_ptr())
+    call("paste_u8", ptr(pre_images), ptr(out_labels), ptr(ranges), ptr(desc_t), n, ptr(out_images), S_h, S_w, max_labels,
+         stream_ptr())
+    return out_images, out_labels, counts, ranges
+
+
+def _paste_staging(cache, n, S_h, S_w, max_labels, dev):
+    """The buffers the augmentation's two launches write when copy-paste follows, kept in ``cache`` (a dict of the caller's or the
+    transform's) per (n, S_h, S_w, max_labels, device)."""
+    key = (n, S_h, S_w, max_labels, str(dev))
+    if cache is None or key not in cache:
+        bufs = (torch.empty(n, 3, S_h, S_w, dtype=torch.float32, device=dev),
+                torch.empty(n, max_labels, 51, dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.int32, device=dev))
+        if cache is None:
+            return bufs
+        cache[key] = bufs
+    return cache[key]
+
+
 def tile_layout(params, i, sizes, input_size):
     """The tiles of output image i: list of (source index, rw, rh, (lx1, ly1, lx2, ly2), padw, padh).  Mosaic: quadrant q
     (bit 0 = right, bit 1 = bottom) holds its source, resized to (rw, rh), with the corner that touches the mosaic centre
@@ -250,9 +368,12 @@ def _rot(dev):
 
 
 def mosaic_batch(images, targets, params, input_size, max_labels=50, out_images=None, out_labels=None, min_margin=2.0,
-                 device="cuda:0"):
+                 device="cuda:0", paste_ioa=0.30, paste_staging=None):
     """images: list of uint8 [h,w,3] arrays / tensors; targets: list of [k,51] normalised label rows; params: ``AugParams``.
-    Returns (images [n,3,S_h,S_w] fp32, labels [n,max_labels,51] fp32, survivors per image [n] int32) on the device."""
+    Returns (images [n,3,S_h,S_w] fp32, labels [n,max_labels,51] fp32, survivors per image [n] int32) on the device.
+    With ``params.paste`` set on any image the two launches write staging buffers (kept in the dict ``paste_staging`` per shape, if
+    one is given) and the copy-paste post-pass (``paste_batch``, IoA threshold ``paste_ioa``) writes the outputs; the count then
+    includes the pasted rows.  With it set on none the calls are those of a batch without the fields."""
     _lib.require_gpu()
     n = len(images)
     if params.n != n or len(targets) != n:
@@ -266,6 +387,11 @@ def mosaic_batch(images, targets, params, input_size, max_labels=50, out_images=
     counts = torch.empty(n, dtype=torch.int32, device=dev)
     if n == 0:
         return out_images, out_labels, counts
+    final = None
+    if bool(np.asarray(params.paste).any()):
+        desc = paste_descriptors(params)                                           # refuses a partner outside the batch before any launch
+        final = (out_images, out_labels, counts)
+        out_images, out_labels, counts = _paste_staging(paste_staging, n, S_h, S_w, max_labels, dev)
     flat, offs, sizes, off = [], [], [], 0
     for im in images:
         im = im if isinstance(im, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(im))
@@ -323,13 +449,16 @@ def mosaic_batch(images, targets, params, input_size, max_labels=50, out_images=
                  ptr(mi_t, lo * 16), ptr(md_t, lo * 12), hi - lo, ptr(out_images, lo * 3 * S_h * S_w), S_h, S_w, stream_ptr())
         call("augment_mix_labels", ptr(dbl_t, n * 28), ptr(tiles_t), ptr(dbl_t), ptr(dbl_t, n * 12), ptr(flags_t), ptr(mi_t), ptr(md_t),
              ptr(rot), n, S_h, S_w, float(min_margin), ptr(out_labels), ptr(counts), max_labels, stream_ptr())
-        return out_images, out_labels, counts
-    for lo in range(0, n, 65535):
-        hi = min(n, lo + 65535)
-        call("augment_u8", ptr(buf), ptr(tiles_t, lo * 64), ptr(dbl_t, lo * 12), ptr(dbl_t, n * 12 + lo * 16), ptr(flags_t, lo * 2),
-             hi - lo, ptr(out_images, lo * 3 * S_h * S_w), S_h, S_w, stream_ptr())
-    call("augment_labels", ptr(dbl_t, n * 28), ptr(tiles_t), ptr(dbl_t), ptr(dbl_t, n * 12), ptr(flags_t), ptr(rot), n, S_h, S_w,
-         float(min_margin), ptr(out_labels), ptr(counts), max_labels, stream_ptr())
+    else:
+        for lo in range(0, n, 65535):
+            hi = min(n, lo + 65535)
+            call("augment_u8", ptr(buf), ptr(tiles_t, lo * 64), ptr(dbl_t, lo * 12), ptr(dbl_t, n * 12 + lo * 16), ptr(flags_t, lo * 2),
+                 hi - lo, ptr(out_images, lo * 3 * S_h * S_w), S_h, S_w, stream_ptr())
+        call("augment_labels", ptr(dbl_t, n * 28), ptr(tiles_t), ptr(dbl_t), ptr(dbl_t, n * 12), ptr(flags_t), ptr(rot), n, S_h, S_w,
+             float(min_margin), ptr(out_labels), ptr(counts), max_labels, stream_ptr())
+    if final is not None:
+        return paste_batch(out_images, out_labels, counts, desc, min_margin=min_margin, ioa_thr=paste_ioa, out_images=final[0],
+                           out_labels=final[1], counts=final[2], check=False)[:3]
     return out_images, out_labels, counts
 
 
@@ -338,23 +467,31 @@ class MosaicTransform(TrainTransform):
     unchanged.  ``enabled = False`` makes it the plain transform (the last ``no_aug_epochs`` of a YOLOX run).
     ``set_position(epoch, it)`` reseeds the generator from (seed, epoch, it): the batch at a data position gets the same
     parameters whenever it is produced, so a resumed run reproduces the batches it would have seen.  ``mixup_prob > 0`` adds
-    mixup (``sample_mixup``, from a generator of its own at the same position); with 0 the transform is what it is without."""
+    mixup (``sample_mixup``, from a generator of its own at the same position); with 0 the transform is what it is without.
+    ``copy_paste_prob > 0`` adds copy-paste (``sample_paste``, a third generator at the same position): an image pastes objects of
+    another image of the batch, each selected with ``copy_paste_obj_prob``, where they hide less than ``copy_paste_ioa`` of every
+    object already there; with 0 the transform is what it is without."""
 
     def __init__(self, max_labels=50, flip_prob=0.5, hsv_prob=1.0, mosaic_prob=1.0, degrees=10.0, translate=0.1,
                  mosaic_scale=(0.5, 1.5), shear=2.0, min_margin=2.0, seed=0, enabled=True, mixup_prob=0.0,
-                 mixup_scale=(0.5, 1.5)):
+                 mixup_scale=(0.5, 1.5), copy_paste_prob=0.0, copy_paste_obj_prob=0.5, copy_paste_ioa=0.30):
         super().__init__(max_labels=max_labels, flip_prob=flip_prob, hsv_prob=hsv_prob, seed=seed)
         self.hsv_prob, self.mosaic_prob, self.degrees, self.translate = hsv_prob, mosaic_prob, degrees, translate
         self.mosaic_scale, self.shear, self.min_margin = tuple(mosaic_scale), shear, min_margin
         self.seed, self.enabled = int(seed), enabled
         self.mixup_prob, self.mixup_scale = mixup_prob, tuple(mixup_scale)
+        self.copy_paste_prob, self.copy_paste_obj_prob, self.copy_paste_ioa = copy_paste_prob, copy_paste_obj_prob, copy_paste_ioa
+        self._paste_staging = {}
         self.last_params = self.last_counts = None
         self.set_position(0, 0)
 
     @classmethod
-    def from_exp(cls, exp, max_labels=50, seed=0, mixup=False):
-        """``mixup=True`` reads the Exp's ``mixup_prob`` / ``mixup_scale`` (``train_24p.py --mixup``); otherwise mixup stays off."""
+    def from_exp(cls, exp, max_labels=50, seed=0, mixup=False, copy_paste=False):
+        """``mixup=True`` reads the Exp's ``mixup_prob`` / ``mixup_scale`` (``train_24p.py --mixup``); otherwise mixup stays off.
+        ``copy_paste=True`` reads the Exp's ``copy_paste_prob`` (``train_24p.py --copy-paste``); otherwise copy-paste stays off."""
         extra = dict(mixup_prob=exp.mixup_prob, mixup_scale=exp.mixup_scale) if mixup else {}
+        if copy_paste:
+            extra["copy_paste_prob"] = exp.copy_paste_prob
         return cls(max_labels=max_labels, flip_prob=exp.flip_prob, hsv_prob=exp.hsv_prob, mosaic_prob=exp.mosaic_prob,
                    degrees=exp.degrees, translate=exp.translate, mosaic_scale=exp.mosaic_scale, shear=exp.shear, seed=seed, **extra)
 
@@ -362,6 +499,7 @@ class MosaicTransform(TrainTransform):
         self.position = (int(epoch), int(it))
         self._aug_rng = position_rng(self.seed, epoch, it)
         self._mix_rng = mixup_rng(self.seed, epoch, it)
+        self._paste_rng = paste_rng(self.seed, epoch, it)
 
     def sample(self, sizes, input_dim, label_counts=None):
         """The parameters of the next batch; mixup needs ``label_counts`` (label rows per source) and is left off without."""
@@ -370,6 +508,8 @@ class MosaicTransform(TrainTransform):
                           flip_prob=self.flip_prob, hsv_prob=self.hsv_prob)
         if self.mixup_prob > 0 and label_counts is not None:
             sample_mixup(self._mix_rng, p, sizes, label_counts, input_dim, mixup_prob=self.mixup_prob, mixup_scale=self.mixup_scale)
+        if self.copy_paste_prob > 0:
+            sample_paste(self._paste_rng, p, len(sizes), input_dim, self.copy_paste_prob, obj_prob=self.copy_paste_obj_prob)
         return p
 
     def batch(self, images, targets, input_dim, out_images=None, out_labels=None):
@@ -379,6 +519,7 @@ class MosaicTransform(TrainTransform):
         params = self.sample([tuple(im.shape[:2]) for im in images], input_dim,
                              [np.asarray(t).size // 51 for t in targets])
         imgs, labs, counts = mosaic_batch(images, targets, params, input_dim, self.max_labels, out_images, out_labels,
-                                          min_margin=self.min_margin)
+                                          min_margin=self.min_margin, paste_ioa=self.copy_paste_ioa,
+                                          paste_staging=self._paste_staging)
         self.last_params, self.last_counts = params, counts
         return imgs, labs

@@ -37,6 +37,9 @@ class Exp(BaseExp):
         self.enable_mixup = True         # with train_24p.py --mixup (ep24.augment.sample_mixup); stock YOLOX's names and values
         self.mixup_prob = 1.0
         self.mixup_scale = (0.5, 1.5)
+        # copy-paste of 24-point objects between the images of a batch (ep24.augment.sample_paste).  A deviation: the reference has no
+        # such attribute (stock YOLOX has no copy-paste; the rule is YOLOv5's copy_paste).  train_24p.py --copy-paste [P] sets it.
+        self.copy_paste_prob = 0.0
         # training
         self.warmup_epochs = 5
         self.max_epoch = 300

@@ -75,6 +75,7 @@ class Trainer:
         if args.augment and not args.raw_u8:
             raise SystemExit("train_24p.py: --augment works on the raw uint8 batches behind the prefetcher (drop --no-prefetch / --fp32-batches)")
         check_mixup_args(args)
+        check_copy_paste_args(args)
         check_multiscale_args(args, exp, self.world)
         if args.fisheye_theta is not None:
             check_fisheye_args(args)
@@ -340,11 +341,16 @@ class Trainer:
         """--augment: ONE ``MosaicTransform`` for the run (the Exp's mosaic_prob / degrees / translate / mosaic_scale / shear /
         flip_prob / hsv_prob), switched on for epochs < max_epoch - no_aug_epochs and off after - what ``no_aug_epochs`` means in
         YOLOX (core/trainer.py before_epoch: close_mosaic).  --mixup adds the Exp's mixup_prob / mixup_scale iff exp.enable_mixup;
-        mixup goes off with the rest."""
+        mixup goes off with the rest.  --copy-paste [P] sets the Exp's copy_paste_prob to P and adds copy-paste; it goes off with
+        the rest too."""
         if getattr(self, "transform", None) is None:
             from datasets import MosaicTransform
             mixup = bool(getattr(self.args, "mixup", False) and self.exp.enable_mixup)
-            self.transform = MosaicTransform.from_exp(self.exp, max_labels=50, seed=self.args.augment_seed, mixup=mixup)
+            paste = float(getattr(self.args, "copy_paste", 0.0) or 0.0)
+            if paste > 0:
+                self.exp.copy_paste_prob = paste
+            self.transform = MosaicTransform.from_exp(self.exp, max_labels=50, seed=self.args.augment_seed, mixup=mixup,
+                                                      copy_paste=paste > 0)
         self.transform.enabled = self.epoch < self.max_epoch - self.exp.no_aug_epochs
         return self.transform
 
@@ -410,6 +416,17 @@ def check_mixup_args(args):
     """--mixup blends a second image into the mosaic images of --augment: it needs --augment."""
     if getattr(args, "mixup", False) and not args.augment:
         raise SystemExit("train_24p.py: --mixup blends a second image into the mosaic of --augment (add --augment)")
+
+
+def check_copy_paste_args(args):
+    """--copy-paste pastes objects between the images that --augment produced: it needs --augment, and a probability in (0, 1]."""
+    p = getattr(args, "copy_paste", 0.0) or 0.0
+    if not p:
+        return
+    if not 0.0 < p <= 1.0:
+        raise SystemExit("train_24p.py: --copy-paste %r: the probability that an image pastes objects, in (0, 1]" % p)
+    if not args.augment:
+        raise SystemExit("train_24p.py: --copy-paste pastes objects of the batch into the images of --augment (add --augment)")
 
 
 def check_multiscale_args(args, exp, world):
@@ -488,6 +505,10 @@ def make_parser():
     p.add_argument("--mixup", action="store_true", help="with --augment: mixup on the GPU (a second image of the batch, letterboxed, "
                    "jittered, mirrored and cropped, averaged into every mosaic image; its 24-point labels re-cast and appended) with the "
                    "Exp's mixup_prob / mixup_scale, iff exp.enable_mixup")
+    p.add_argument("--copy-paste", nargs="?", const=0.5, default=0.0, type=float, metavar="P", help="with --augment: copy-paste on the GPU "
+                   "(YOLOv5's copy_paste for 24-point labels): with probability P (0.5 when the flag stands alone) an image pastes objects "
+                   "of another image of the batch, shifted and possibly mirrored, where they hide less than 30 %% of every object already "
+                   "there; their polygons are the masks.  Off when absent; goes off with the rest at no_aug_epochs")
     p.add_argument("--multiscale", action="store_true", help="stock YOLOX's multiscale training: a new input size from exp.random_resize "
                    "(multiples of 32 within exp.multiscale_range of input_size / 32) every --multiscale-interval steps, the batch and "
                    "its labels resized on the GPU behind loader and augmentation, one captured step per size; single process, captured step only")

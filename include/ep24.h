@@ -984,6 +984,41 @@ int ep24_augment_mix_u8(const uint8_t* images, const int64_t* tiles, const doubl
 int ep24_augment_mix_labels(const double* rows, const int64_t* tiles, const double* tile_scales, const double* params,
                             const int32_t* flags, const int64_t* mix, const double* mix_scales, const double* rot, int n, int S_h,
                             int S_w, double min_margin, float* out, int32_t* out_count, int max_labels, void* stream);
+/* Copy-paste (YOLOv5 / v8 copy_paste; csrc/paste.hip): a post-pass of two launches over the batch the launches
+ * above produced.  The 24-gon of a label row is the object's mask.  Conventions as above: pixel x covers [x, x+1), its centre is
+ * x + 0.5; labels [n][max_labels][51] fp32 rows (class, cx, cy, 24 x (x, y)) in output pixels; images [n,3,S_h,S_w] fp32.
+ *   paste[n][8] int64 = {0 on, 1 partner j (0 <= j < n, j == i allowed), 2 flip, 3 dx, 4 dy, 5 select (bit k = candidate k may be
+ *       pasted), 6, 7 reserved (0)}.  Image i takes objects of image j through the rigid integer transform
+ *       point (X, Y) -> ((flip ? S_w - X : X) + dx, Y + dy);  output pixel (x, y) reads source pixel (xs, ys) with xu = x - dx,
+ *       xs = flip ? S_w - 1 - xu : xu, ys = y - dy.  No resampling.
+ * ep24_paste_labels: pre_labels / pre_count are the label launch's outputs for the whole batch, a snapshot (out_labels is another
+ * buffer).  With E = min(pre_count[i], max_labels): out_labels[i][0:E] = pre_labels[i][0:E] bit for bit, the rest zero,
+ * out_count[i] = pre_count[i], paste_range[n][2] int32 = {E, E}.  With on != 0 and pre_count[i] <= max_labels the candidates are
+ * rows k = 0 .. min(pre_count[j], max_labels) - 1 of pre_labels[j], in that order, until the image holds max_labels rows.  The
+ * transformed coordinates are evaluated in double on the fp32 inputs as written above and rounded once to fp32; those fp32 values
+ * are what is tested and stored.  Candidate k is skipped if bit k of select is clear (k >= 64: always), if its centre is not at
+ * least min_margin inside [0,S_w] x [0,S_h], if one of its 24 vertices is outside that closed rectangle, or if some row q among the
+ * image's E rows and the candidates accepted before it has area(q) > 0 and inter(cand, q) / area(q) >= ioa_thr (inter: poly24.h's
+ * trapezoid-decomposition intersection, area: the absolute shoelace area, both in double from the fp32 vertices; one division).
+ * Otherwise it is appended as (class, transformed centre, vertices); with flip, source vertex k becomes vertex (12 - k) mod 24 (the
+ * mirrored ray of 15k degrees is the ray of 180 - 15k degrees), so the row stays ordered by ray.  out_count[i] and
+ * paste_range[i][1] grow by one per accepted candidate.  Acceptance is sequential per image: the result is a deterministic
+ * function of the inputs.  The descriptor lives in device memory, so the library cannot refuse a partner outside [0, n): the
+ * host side that builds it does (ep24.augment.paste_descriptors raises with EP24_E_ARG), and the kernels treat such a descriptor
+ * as on == 0.  EP24_E_ARG: n < 0, a null pointer with n > 0, max_labels outside 1 .. 256, ioa_thr <= 0, min_margin < 0,
+ * out_labels == pre_labels.  n == 0 is EP24_OK; n is cut into launches of 65 535 inside the call. */
+int ep24_paste_labels(const float* pre_labels, const int32_t* pre_count, const int64_t* paste, int n, int S_h, int S_w,
+                      double min_margin, double ioa_thr, float* out_labels, int32_t* out_count, int32_t* paste_range, int max_labels,
+                      void* stream);
+/* The image half, bit exact (fp32 in, fp32 out, no arithmetic on pixel values); every output word is written; out_images !=
+ * pre_images.  Pixel (x, y) of image i is pre_images[j][c][ys][xs] if on, (xs, ys) is inside the image and the point
+ * (x + 0.5, y + 0.5) is inside at least one row of out_labels[i][paste_range[i][0] : paste_range[i][1]] by the crossing rule of
+ * ep24_poly24_raster (csrc/raster_rule.h, vertices promoted to double); otherwise it is pre_images[i][c][y][x].  A row with a NaN
+ * or infinite coordinate pastes nothing (ep24_paste_labels never writes one).  Tiles of 64 x 16 pixels that no pasted row's vertex
+ * box meets are a plain copy.  S_w % 4 == 0 with 16-byte aligned buffers moves four pixels per access; any other shape runs pixel
+ * by pixel. */
+int ep24_paste_u8(const float* pre_images, const float* out_labels, const int32_t* paste_range, const int64_t* paste, int n,
+                  float* out_images, int S_h, int S_w, int max_labels, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * C4  swapped backbones (yolox_24p/models/darknet.py:179-429, yolox/models/yolo_pafpn.py:31-38; BASELINE config 4)
