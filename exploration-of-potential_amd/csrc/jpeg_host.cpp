@@ -1,0 +1,355 @@
+// ep24 - host entropy stage of the JPEG decoder (include/ep24_jpeg.h): marker parser and table-driven baseline Huffman decoder.
+// Host compiler only: no HIP, no device code - the loader processes load this library without opening the GPU.
+//
+// Every read of the file goes through a position that is checked against n; every write goes to coef_out below ncoef (<= capacity)
+// or into the header; a block decodes in at most 64 steps whatever the bits say, so corrupt input ends in EP24JPEG_E_DATA.
+#include <stdarg.h>
+#include <stdio.h>
+#include <string.h>
+
+#include "../../include/ep24_jpeg.h"
+
+namespace {
+
+thread_local char g_err[256] = "";
+
+int fail(int code, const char* fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_err, sizeof(g_err), fmt, ap);
+    va_end(ap);
+    return code;
+}
+
+const uint8_t kZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
+                             41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
+                             30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+
+enum { LOOK = 9 };
+
+struct Huff {
+    bool defined;
+    int nvals;
+    uint8_t vals[256];
+    uint16_t look[1 << LOOK];      // (length << 8) | symbol for codes of at most LOOK bits, 0 otherwise
+    int32_t maxcode[17];           // largest code of each length, -1: none
+    int32_t valoff[17];            // vals index = code + valoff[length]
+};
+
+struct Parsed {
+    ep24jpeg_header hd;
+    int tq[3], td[3], ta[3], id[3];
+    int mcus_x, mcus_y;
+    int64_t scan_pos;
+    Huff dc[4], ac[4];
+};
+
+int build_huff(Huff& h, const uint8_t* bits, const uint8_t* vals, int nvals) {
+    h.defined = true;
+    h.nvals = nvals;
+    memcpy(h.vals, vals, (size_t)nvals);
+    memset(h.look, 0, sizeof(h.look));
+    int32_t code = 0;
+    int k = 0;
+    for (int l = 1; l <= 16; ++l) {
+        h.valoff[l] = k - code;
+        const int cnt = bits[l - 1];
+        if (code + cnt > (1 << l)) return fail(EP24JPEG_E_DATA, "jpeg: a Huffman table has more codes of length %d than fit", l);
+        if (l <= LOOK)
+            for (int i = 0; i < cnt; ++i) {
+                const int lo = (code + i) << (LOOK - l);
+                for (int j = 0; j < (1 << (LOOK - l)); ++j) h.look[lo + j] = (uint16_t)((l << 8) | vals[k + i]);
+            }
+        code += cnt;
+        k += cnt;
+        h.maxcode[l] = cnt ? code - 1 : -1;
+        code <<= 1;
+    }
+    return EP24JPEG_OK;
+}
+
+inline int u16(const uint8_t* d, int64_t p) { return (d[p] << 8) | d[p + 1]; }
+
+int parse(const uint8_t* d, int64_t n, Parsed& P) {
+    memset(&P.hd, 0, sizeof(P.hd));
+    for (int i = 0; i < 4; ++i) P.dc[i].defined = P.ac[i].defined = false;
+    if (!d || n < 4 || d[0] != 0xFF || d[1] != 0xD8) return fail(EP24JPEG_E_DATA, "jpeg: not a JPEG file (no SOI marker)");
+    uint16_t qt[4][64];
+    bool qt_def[4] = {false, false, false, false}, have_frame = false;
+    int64_t p = 2;
+    for (;;) {
+        if (p + 2 > n) return fail(EP24JPEG_E_DATA, "jpeg: the file ends before the scan (offset %lld)", (long long)p);
+        if (d[p] != 0xFF) return fail(EP24JPEG_E_DATA, "jpeg: marker expected at offset %lld", (long long)p);
+        while (p < n && d[p] == 0xFF) ++p;             // fill bytes
+        if (p >= n) return fail(EP24JPEG_E_DATA, "jpeg: the file ends inside a marker");
+        const int m = d[p++];
+        if (m == 0xD8 || (m >= 0xD0 && m <= 0xD7) || m == 0x01) continue;       // no parameters
+        if (m == 0xD9) return fail(EP24JPEG_E_DATA, "jpeg: EOI before any scan");
+        if (m == 0x00) return fail(EP24JPEG_E_DATA, "jpeg: stuffed byte outside a scan");
+        if (p + 2 > n) return fail(EP24JPEG_E_DATA, "jpeg: the file ends inside a segment header");
+        const int L = u16(d, p);
+        if (L < 2 || p + L > n) return fail(EP24JPEG_E_DATA, "jpeg: segment FF%02X of length %d runs past the end of the file", m, L);
+        const uint8_t* s = d + p + 2;
+        const int sl = L - 2;
+        const int64_t end = p + L;
+        if (m == 0xDB) {
+            int q = 0;
+            while (q < sl) {
+                const int pq = s[q] >> 4, t = s[q] & 15;
+                const int need = pq ? 129 : 65;
+                if (pq > 1 || t > 3 || q + need > sl) return fail(EP24JPEG_E_DATA, "jpeg: bad quantisation table segment");
+                for (int k = 0; k < 64; ++k) qt[t][kZigzag[k]] = (uint16_t)(pq ? u16(s, q + 1 + 2 * k) : s[q + 1 + k]);
+                qt_def[t] = true;
+                q += need;
+            }
+        } else if (m == 0xC4) {
+            int q = 0;
+            while (q < sl) {
+                if (q + 17 > sl) return fail(EP24JPEG_E_DATA, "jpeg: bad Huffman table segment");
+                const int tc = s[q] >> 4, th = s[q] & 15;
+                int cnt = 0;
+                for (int i = 0; i < 16; ++i) cnt += s[q + 1 + i];
+                if (tc > 1 || th > 3 || cnt > 256 || q + 17 + cnt > sl) return fail(EP24JPEG_E_DATA, "jpeg: bad Huffman table segment");
+                const int rc = build_huff(tc ? P.ac[th] : P.dc[th], s + q + 1, s + q + 17, cnt);
+                if (rc) return rc;
+                q += 17 + cnt;
+            }
+        } else if (m == 0xC0 || m == 0xC1) {
+            if (have_frame) return fail(EP24JPEG_E_DATA, "jpeg: a second frame header");
+            if (sl < 6) return fail(EP24JPEG_E_DATA, "jpeg: short frame header");
+            if (s[0] != 8) return fail(EP24JPEG_E_UNSUPPORTED, "jpeg: %d-bit sample precision is not supported (8-bit only)", s[0]);
+            ep24jpeg_header& h = P.hd;
+            h.height = u16(s, 1);
+            h.width = u16(s, 3);
+            h.ncomp = s[5];
+            if (h.ncomp != 1 && h.ncomp != 3)
+                return fail(EP24JPEG_E_UNSUPPORTED, "jpeg: %d components are not supported (1 or 3; CMYK / YCCK files have 4)", h.ncomp);
+            if (sl < 6 + 3 * h.ncomp) return fail(EP24JPEG_E_DATA, "jpeg: short frame header");
+            if (h.width < 1 || h.height < 1) return fail(EP24JPEG_E_DATA, "jpeg: empty image (%d x %d)", h.width, h.height);
+            if (h.width > EP24JPEG_MAX_SIDE || h.height > EP24JPEG_MAX_SIDE)
+                return fail(EP24JPEG_E_UNSUPPORTED, "jpeg: %d x %d is above the supported side of %d", h.width, h.height, EP24JPEG_MAX_SIDE);
+            for (int i = 0; i < h.ncomp; ++i) {
+                P.id[i] = s[6 + 3 * i];
+                h.h[i] = s[7 + 3 * i] >> 4;
+                h.v[i] = s[7 + 3 * i] & 15;
+                P.tq[i] = s[8 + 3 * i];
+                if (P.tq[i] > 3 || h.h[i] < 1 || h.v[i] < 1) return fail(EP24JPEG_E_DATA, "jpeg: bad component %d in the frame header", i);
+            }
+            if (h.ncomp == 1) {
+                h.h[0] = h.v[0] = 1;                   // a one-component scan is not interleaved: its MCU is one block
+            } else {
+                const bool luma = (h.h[0] == 1 && h.v[0] == 1) || (h.h[0] == 2 && h.v[0] == 1) || (h.h[0] == 2 && h.v[0] == 2);
+                if (!luma || h.h[1] != 1 || h.v[1] != 1 || h.h[2] != 1 || h.v[2] != 1)
+                    return fail(EP24JPEG_E_UNSUPPORTED, "jpeg: sampling %dx%d,%dx%d,%dx%d is not supported (luma 1x1, 2x1 or 2x2 with chroma 1x1)",
+                                h.h[0], h.v[0], h.h[1], h.v[1], h.h[2], h.v[2]);
+            }
+            have_frame = true;
+        } else if (m == 0xC2 || m == 0xC6 || m == 0xCA || m == 0xCE) {
+            return fail(EP24JPEG_E_UNSUPPORTED, "jpeg: progressive files (SOF%d) are not supported (baseline only)", m - 0xC0);
+        } else if (m >= 0xC9 && m <= 0xCF && m != 0xCC) {
+            return fail(EP24JPEG_E_UNSUPPORTED, "jpeg: arithmetic coding (SOF%d) is not supported", m - 0xC0);
+        } else if (m == 0xCC) {
+            return fail(EP24JPEG_E_UNSUPPORTED, "jpeg: arithmetic coding (DAC segment) is not supported");
+        } else if (m == 0xC3 || m == 0xC5 || m == 0xC7) {
+            return fail(EP24JPEG_E_UNSUPPORTED, "jpeg: lossless / hierarchical files (SOF%d) are not supported", m - 0xC0);
+        } else if (m == 0xDD) {
+            if (sl < 2) return fail(EP24JPEG_E_DATA, "jpeg: short DRI segment");
+            P.hd.restart_interval = u16(s, 0);
+        } else if (m == 0xDA) {
+            if (!have_frame) return fail(EP24JPEG_E_DATA, "jpeg: a scan before the frame header");
+            ep24jpeg_header& h = P.hd;
+            if (sl < 1) return fail(EP24JPEG_E_DATA, "jpeg: short scan header");
+            const int ns = s[0];
+            if (ns != h.ncomp)
+                return fail(EP24JPEG_E_UNSUPPORTED, "jpeg: more than one scan (the first holds %d of %d components) is not supported", ns, h.ncomp);
+            if (sl < 1 + 2 * ns + 3) return fail(EP24JPEG_E_DATA, "jpeg: short scan header");
+            for (int i = 0; i < ns; ++i) {
+                if (s[1 + 2 * i] != P.id[i]) return fail(EP24JPEG_E_DATA, "jpeg: scan component %d does not follow the frame's order", i);
+                P.td[i] = s[2 + 2 * i] >> 4;
+                P.ta[i] = s[2 + 2 * i] & 15;
+                if (P.td[i] > 3 || P.ta[i] > 3 || !P.dc[P.td[i]].defined || !P.ac[P.ta[i]].defined)
+                    return fail(EP24JPEG_E_DATA, "jpeg: component %d uses a Huffman table that was not defined", i);
+                if (!qt_def[P.tq[i]]) return fail(EP24JPEG_E_DATA, "jpeg: component %d uses a quantisation table that was not defined", i);
+                memcpy(h.qt[i], qt[P.tq[i]], sizeof(h.qt[i]));
+            }
+            if (s[1 + 2 * ns] != 0 || s[2 + 2 * ns] != 63 || s[3 + 2 * ns] != 0)
+                return fail(EP24JPEG_E_UNSUPPORTED, "jpeg: a scan with spectral selection / successive approximation is not supported");
+            int hmax = 1, vmax = 1;
+            for (int i = 0; i < h.ncomp; ++i) {
+                if (h.h[i] > hmax) hmax = h.h[i];
+                if (h.v[i] > vmax) vmax = h.v[i];
+            }
+            P.mcus_x = (h.width + 8 * hmax - 1) / (8 * hmax);
+            P.mcus_y = (h.height + 8 * vmax - 1) / (8 * vmax);
+            h.ncoef = 0;
+            for (int i = 0; i < h.ncomp; ++i) {
+                h.blocks_w[i] = P.mcus_x * h.h[i];
+                h.blocks_h[i] = P.mcus_y * h.v[i];
+                h.nblocks[i] = (int64_t)h.blocks_w[i] * h.blocks_h[i];
+                h.ncoef += 64 * h.nblocks[i];
+            }
+            P.scan_pos = end;
+            return EP24JPEG_OK;
+        }                                                 // APPn, COM and everything else with a length: skipped
+        p = end;
+    }
+}
+
+struct Bits {
+    const uint8_t* d;
+    int64_t p, end;
+    uint64_t acc;
+    int n;          // unread bits in acc
+    int pad;        // of them (at the low end), zero bits made up after the data ended; pad > n: made-up bits were consumed
+    bool stop;      // a marker (or the end of the file) was reached
+};
+
+inline void fill(Bits& b) {
+    // four bytes at once while none of them is 0xFF (no stuffing, no marker) and the file has them
+    if (b.n <= 32 && !b.stop && b.p + 4 <= b.end) {
+        uint32_t w;
+        memcpy(&w, b.d + b.p, 4);
+        const uint32_t inv = ~w;                          // a 0xFF byte of w is a zero byte of inv
+        if (!((inv - 0x01010101u) & ~inv & 0x80808080u)) {
+            b.acc = (b.acc << 32) | __builtin_bswap32(w);
+            b.n += 32;
+            b.p += 4;
+            return;
+        }
+    }
+    while (b.n <= 56) {
+        unsigned v = 0;
+        if (!b.stop && b.p < b.end) {
+            v = b.d[b.p];
+            if (v == 0xFF) {
+                if (b.p + 1 < b.end && b.d[b.p + 1] == 0) {
+                    b.p += 2;
+                } else {
+                    b.stop = true;
+                    v = 0;
+                    b.pad += 8;
+                }
+            } else {
+                ++b.p;
+            }
+        } else {
+            b.stop = true;
+            b.pad += 8;
+        }
+        b.acc = (b.acc << 8) | v;
+        b.n += 8;
+    }
+}
+
+// a code (at most 16 bits) and the value behind it (at most 15) are read after ONE refill: the caller keeps 32 bits in the buffer
+inline int decode_symbol(Bits& b, const Huff& h) {
+    const uint32_t w = (uint32_t)(b.acc >> (b.n - 16)) & 0xFFFFu;
+    const uint16_t e = h.look[w >> (16 - LOOK)];
+    if (e) {
+        b.n -= e >> 8;
+        return e & 255;
+    }
+    for (int l = LOOK + 1; l <= 16; ++l) {
+        const int32_t code = (int32_t)(w >> (16 - l));
+        if (code <= h.maxcode[l]) {
+            const int idx = code + h.valoff[l];
+            if (idx < 0 || idx >= h.nvals) return -1;
+            b.n -= l;
+            return h.vals[idx];
+        }
+    }
+    return -1;
+}
+
+// s bits (1 .. 15) as a signed value: EXTEND(v, s) = v if v >= 2^(s-1) else v - 2^s + 1
+inline int receive_extend(Bits& b, int s) {
+    const int v = (int)((b.acc >> (b.n - s)) & ((1u << s) - 1));
+    b.n -= s;
+    // without a branch (the sign of a coefficient is a coin toss): all ones when v is below 2^(s-1)
+    const int below = (v - (1 << (s - 1))) >> 31;
+    return v + (below & (1 - (1 << s)));
+}
+
+}  // namespace
+
+extern "C" int ep24jpeg_abi_version(void) { return EP24JPEG_ABI_VERSION; }
+extern "C" const char* ep24jpeg_last_error(void) { return g_err; }
+
+extern "C" int ep24jpeg_parse(const uint8_t* bytes, int64_t n, ep24jpeg_header* header_out) {
+    if (!bytes || !header_out || n < 0) return fail(EP24JPEG_E_ARG, "ep24jpeg_parse: null pointer or negative length");
+    Parsed P;
+    const int rc = parse(bytes, n, P);
+    if (rc) return rc;
+    *header_out = P.hd;
+    return EP24JPEG_OK;
+}
+
+extern "C" int ep24jpeg_entropy_decode(const uint8_t* bytes, int64_t n, int16_t* coef_out, int64_t capacity) {
+    if (!bytes || !coef_out || n < 0) return fail(EP24JPEG_E_ARG, "ep24jpeg_entropy_decode: null pointer or negative length");
+    Parsed P;
+    int rc = parse(bytes, n, P);
+    if (rc) return rc;
+    const ep24jpeg_header& h = P.hd;
+    if (capacity < h.ncoef)
+        return fail(EP24JPEG_E_ARG, "ep24jpeg_entropy_decode: capacity %lld below the %lld coefficients of the file", (long long)capacity, (long long)h.ncoef);
+    memset(coef_out, 0, (size_t)h.ncoef * sizeof(int16_t));
+    int16_t* base[3];
+    int64_t off = 0;
+    for (int c = 0; c < h.ncomp; ++c) {
+        base[c] = coef_out + off;
+        off += 64 * h.nblocks[c];
+    }
+    Bits b = {bytes, P.scan_pos, n, 0, 0, 0, false};
+    int pred[3] = {0, 0, 0};
+    const int ri = h.restart_interval;
+    int rst = 0, left = ri;
+    for (int my = 0; my < P.mcus_y; ++my)
+        for (int mx = 0; mx < P.mcus_x; ++mx) {
+            if (ri) {
+                if (left == 0) {
+                    // the bits of the interval end inside the byte in front of the marker, so the reader has stopped at it
+                    int64_t p = b.p;
+                    if (!b.stop) fill(b), p = b.p;
+                    while (p + 1 < n && bytes[p] == 0xFF && bytes[p + 1] == 0xFF) ++p;      // fill bytes
+                    if (!b.stop || p + 1 >= n || bytes[p] != 0xFF || bytes[p + 1] != 0xD0 + rst)
+                        return fail(EP24JPEG_E_DATA, "jpeg: RST%d expected before MCU %d", rst, my * P.mcus_x + mx);
+                    rst = (rst + 1) & 7;
+                    b = Bits{bytes, p + 2, n, 0, 0, 0, false};
+                    pred[0] = pred[1] = pred[2] = 0;
+                    left = ri;
+                }
+                --left;
+            }
+            for (int c = 0; c < h.ncomp; ++c) {
+                const Huff& hdc = P.dc[P.td[c]];
+                const Huff& hac = P.ac[P.ta[c]];
+                for (int by = 0; by < h.v[c]; ++by)
+                    for (int bx = 0; bx < h.h[c]; ++bx) {
+                        int16_t* blk = base[c] + ((int64_t)(my * h.v[c] + by) * h.blocks_w[c] + (mx * h.h[c] + bx)) * 64;
+                        if (b.n < 32) fill(b);
+                        const int t = decode_symbol(b, hdc);
+                        if (t < 0 || t > 11) return fail(EP24JPEG_E_DATA, "jpeg: bad DC code in MCU %d", my * P.mcus_x + mx);
+                        if (t) pred[c] += receive_extend(b, t);
+                        if (pred[c] < -32768 || pred[c] > 32767) return fail(EP24JPEG_E_DATA, "jpeg: DC value out of range in MCU %d", my * P.mcus_x + mx);
+                        blk[0] = (int16_t)pred[c];
+                        for (int k = 1; k < 64;) {
+                            if (b.n < 32) fill(b);
+                            const int rs = decode_symbol(b, hac);
+                            if (rs < 0) return fail(EP24JPEG_E_DATA, "jpeg: bad AC code in MCU %d", my * P.mcus_x + mx);
+                            const int r = rs >> 4, s = rs & 15;
+                            if (s == 0) {
+                                if (r != 15) break;       // end of block
+                                k += 16;
+                                continue;
+                            }
+                            k += r;
+                            if (k > 63) return fail(EP24JPEG_E_DATA, "jpeg: AC run past the end of a block in MCU %d", my * P.mcus_x + mx);
+                            blk[kZigzag[k]] = (int16_t)receive_extend(b, s);
+                            ++k;
+                        }
+                        if (b.pad > b.n) return fail(EP24JPEG_E_DATA, "jpeg: the entropy-coded data ends in MCU %d of %d", my * P.mcus_x + mx, P.mcus_x * P.mcus_y);
+                    }
+            }
+        }
+    return EP24JPEG_OK;
+}

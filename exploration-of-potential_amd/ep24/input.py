@@ -111,6 +111,10 @@ class TrainTransform:
         return self._dist.distort_batch(dev_imgs, None, thetas)[0]
 
     def batch(self, images, targets, input_dim, out_images=None, out_labels=None):
+        """``images``: uint8 [h,w,3] arrays / tensors of any sizes, or entropy-decoded JPEG files (``ep24.jpeg.JpegCoefficients``):
+        those are finished on the GPU first (``ep24.jpeg.finish``, BGR, on the stream this call runs on)."""
+        from .jpeg import finish_mixed
+        images = finish_mixed(images)
         if self.fisheye is not None:
             images = self.warp(images)
         imgs, rs = preproc_batch(images, input_dim, out=out_images)
@@ -125,8 +129,8 @@ class TrainTransform:
 class DataPrefetcher:
     """The reference's prefetcher (data/data_prefetcher.py): the next batch is prepared on a side stream while the
     current step runs; ``next()`` makes the compute stream wait for it.  ``loader`` yields either ready tensors
-    ``(images, labels, info, ids)`` (as the reference's loader does) or raw batches ``(list of uint8 HWC images, list of
-    label rows, info, ids)`` - then ``transform.batch`` (upload + the two preproc launches) runs on the side stream too."""
+    ``(images, labels, info, ids)`` (as the reference's loader does) or raw batches ``(list of uint8 HWC images or of
+    ``ep24.jpeg.JpegCoefficients``, list of label rows, info, ids)`` - then ``transform.batch`` (upload + the two preproc launches) runs on the side stream too."""
 
     def __init__(self, loader, input_size=(640, 640), transform=None):
         _lib.require_gpu()

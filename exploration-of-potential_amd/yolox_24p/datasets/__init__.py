@@ -1,6 +1,6 @@
 """Synthetic stand-in for ``COCO24PDataset`` (datasets/coco24p.py): items are ``(image [3,S,S] fp32 0..255, labels
-[50,51], img_info, img_id)`` exactly as the trainer unpacks them (train_24p.py:83).  The real dataset (cv2.imread of
-hard-coded paths) is outside the hot path; its ``TrainTransform`` / ``preproc`` half is ``ep24.input`` (GPU)
+[50,51], img_info, img_id)`` exactly as the trainer unpacks them (train_24p.py:83).  The real dataset is ``COCO24PFolderDataset``
+(datasets/coco24p.py here: a folder of JPEG files + txt labels, decoded by ``ep24.jpeg``); its ``TrainTransform`` / ``preproc`` half is ``ep24.input`` (GPU)
 and is re-exported here under the reference's names."""
 import _path  # noqa: F401
 import torch
@@ -75,3 +75,4 @@ COCO24PDataset = SyntheticDataset        # name the reference's Exp imports (exp
 
 from ep24.input import TrainTransform, preproc  # noqa: E402,F401   (datasets/data_augment.py:109-174, on the GPU)
 from ep24.augment import MosaicTransform  # noqa: E402,F401   (mosaic / affine / mirror / HSV for 24-point labels, on the GPU)
+from .coco24p import COCO24PFolderDataset  # noqa: E402,F401   (a folder of JPEG files + txt labels; decode split host / GPU: ep24.jpeg)

@@ -1,7 +1,8 @@
 """``Exp``: model / data / optimizer factory of the 24p detector (reference exp/yolox_base.py:11-137) on top of the
 MI355X-native path: ``get_model`` builds the ep24 parameter tree (HIP plan behind ``YOLOX.forward``),
-``get_optimizer`` the fused nesterov SGD, ``get_data_loader`` a synthetic source with the reference's label layout
-(the reference's COCO24P loader reads hard-coded /home/gaoyu/... paths, coco24p.py:19-20, and is out of scope)."""
+``get_optimizer`` the fused nesterov SGD, ``get_data_loader`` a synthetic source with the reference's label layout, or - with
+``data_dir`` / ``label_dir`` set - a folder of JPEG files and txt labels (``datasets.COCO24PFolderDataset``; the reference's
+COCO24P loader reads hard-coded /home/gaoyu/... paths, coco24p.py:19-20)."""
 import _path  # noqa: F401
 import torch.nn as nn
 
@@ -26,6 +27,14 @@ class Exp(BaseExp):
         self.synthetic_len = 64          # images per synthetic epoch
         self.loader_workers = 4          # processes of the synthetic fp32 loader (train_24p.py --loader-workers)
         self.synthetic_gts = 10
+        # a real dataset (datasets.COCO24PFolderDataset): folders of <stem>.jpg and of COCO_24p_label/<stem>.txt; None = the synthetic source.
+        # train_24p.py --data-dir / --label-dir / --val-data-dir / --val-label-dir / --jpeg-decoder set them
+        self.data_dir = None
+        self.label_dir = None
+        self.val_data_dir = None
+        self.val_label_dir = None
+        self.jpeg_decoder = "gpu"        # "gpu": Huffman stage in the loader processes, the rest on the GPU (ep24.jpeg); "pil": Pillow
+        self.data_seed = 0               # seed of the per-epoch shuffle of the folder dataset
         # augmentation (stock YOLOX's names and values; read by train_24p.py --augment only: ep24.augment.MosaicTransform)
         self.mosaic_prob = 1.0
         self.degrees = 10.0
@@ -86,6 +95,8 @@ class Exp(BaseExp):
         from datasets import ResumableSampler, SyntheticDataset, raw_collate
         import torch
         import os
+        if self.data_dir is not None:
+            return self.folder_loader(batch_size, self.data_dir, self.label_dir, train=True, raw_u8=raw_u8, workers=workers, pin=pin)
         self.dataset = SyntheticDataset(self.synthetic_len, tuple(self.input_size), self.synthetic_gts, self.num_classes, raw=raw_u8)
         world, rank = int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("RANK", 0))
         sampler = None
@@ -105,6 +116,32 @@ class Exp(BaseExp):
         if raw_u8:                                        # lists of uint8 images + label rows: letterboxed on the GPU by the prefetcher
             kw["collate_fn"] = raw_collate
         return torch.utils.data.DataLoader(self.dataset, **kw)
+
+    def folder_loader(self, batch_size, data_dir, label_dir, train, raw_u8=True, workers=None, pin=None):
+        """Raw batches of a ``COCO24PFolderDataset``: lists of ``JpegCoefficients`` (or of Pillow's BGR arrays with
+        ``jpeg_decoder = "pil"``) + label rows, from ``data_num_workers`` loader processes (at most 16; ``workers`` overrides) that run
+        the Huffman stage and never open the GPU.  Training: shuffled per epoch from ``data_seed`` by a ``DistributedSampler`` (one
+        rank included, so ``ResumableSampler.set_epoch`` reshuffles), incomplete last batch dropped.  Validation: in order, all kept."""
+        import os
+        import torch
+        from datasets import COCO24PFolderDataset, ResumableSampler, raw_collate
+        from ep24._lib import Ep24Error
+        if not raw_u8:
+            raise Ep24Error("ep24: a folder dataset yields raw batches (images of any sizes), letterboxed on the GPU behind the prefetcher; "
+                            "ready-made fp32 batches are the synthetic source's")
+        if label_dir is None:
+            raise Ep24Error("ep24: data_dir %s is set without a label_dir (train_24p.py --label-dir)" % data_dir)
+        dataset = COCO24PFolderDataset(data_dir, label_dir, decoder=self.jpeg_decoder, report_cuda=getattr(self, "report_loader_cuda", False))
+        workers = min(int(self.data_num_workers if workers is None else workers), 16)
+        kw = dict(batch_size=batch_size, num_workers=workers, collate_fn=raw_collate, pin_memory=bool(pin) if pin is not None else False)
+        if workers > 0:
+            kw.update(persistent_workers=True, prefetch_factor=2)
+        if not train:
+            return torch.utils.data.DataLoader(dataset, shuffle=False, drop_last=False, generator=torch.Generator(), **kw)
+        self.dataset = dataset
+        world, rank = int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("RANK", 0))
+        sampler = torch.utils.data.distributed.DistributedSampler(dataset, num_replicas=world, rank=rank, shuffle=True, seed=int(self.data_seed))
+        return torch.utils.data.DataLoader(dataset, sampler=ResumableSampler(sampler), drop_last=True, **kw)
 
     def random_resize(self, data_loader=None, epoch=None, rng=None):
         """A multiscale input size, multiple of 32, aspect ratio of input_size (exp/yolox_base.py:93-107); plans are cached per size.
@@ -154,6 +191,8 @@ class Exp(BaseExp):
         ``(images, label rows, info, ids)`` can take its place."""
         import torch
         from datasets import SyntheticDataset, raw_collate
+        if self.val_data_dir is not None:
+            return self.folder_loader(batch_size, self.val_data_dir, self.val_label_dir, train=False)
         ds = SyntheticDataset(self.eval_len, tuple(self.test_size), self.synthetic_gts, self.num_classes, seed=self.eval_seed, raw=True)
         # a generator of its own: iterating the loader must not draw from the global RNG the training run relies on
         return torch.utils.data.DataLoader(ds, batch_size=batch_size, shuffle=False, num_workers=0, drop_last=False,

@@ -10,7 +10,7 @@ save every image with its 24-point detections drawn on it.
 ``save_eval_results`` / ``vis`` (:266-367) without the host-side OpenCV.  Results go to ``<output_dir>/<timestamp>/``: the drawn
 image under its own name, ``<name>.dets.npy`` with the ``[n, 29]`` float32 rows beside it, and one ``detections.json`` (file, size,
 ratio, count).  ``--save-segm FILE`` also writes every detection of the run as a COCO "segm" result (``ep24.results``: the polygon
-rasterised on the original image and run-length encoded on the GPU).  ``.npy`` (uint8 HWC) and binary PPM are read and written natively; JPEG / PNG when PIL is installed.
+rasterised on the original image and run-length encoded on the GPU).  ``.npy`` (uint8 HWC) and binary PPM are read and written natively; JPEG / PNG when PIL is installed (without it, baseline JPEG files are read through ``ep24.jpeg``).
 """
 import argparse
 import json
@@ -25,6 +25,7 @@ from exp import get_exp
 
 NATIVE_EXT = (".npy", ".ppm")
 PIL_EXT = (".jpg", ".jpeg", ".png", ".bmp")
+JPEG_EXT = (".jpg", ".jpeg")                                # read through ep24.jpeg when PIL is not installed
 
 
 def _pil():
@@ -71,9 +72,14 @@ def read_image(path):
         img = read_ppm(path)
     else:
         Image = _pil()
-        if Image is None:
-            raise SystemExit("show_24p.py: %s needs PIL, which is not installed (.npy and .ppm are read natively)" % path)
-        img = np.asarray(Image.open(path).convert("RGB"))
+        if Image is None and ext in JPEG_EXT:               # without PIL: the project's own baseline decoder (host Huffman stage + GPU)
+            from ep24 import jpeg
+            with open(path, "rb") as fh:
+                img = jpeg.decode([fh.read()], bgr=False)[0].cpu().numpy()
+        elif Image is None:
+            raise SystemExit("show_24p.py: %s needs PIL, which is not installed (.npy, .ppm and baseline .jpg are read natively)" % path)
+        else:
+            img = np.asarray(Image.open(path).convert("RGB"))
     if img.ndim != 3 or img.shape[2] != 3 or img.dtype != np.uint8:
         raise SystemExit("show_24p.py: %s is not a uint8 [h, w, 3] image (got %s %s)" % (path, img.shape, img.dtype))
     return np.ascontiguousarray(img)
@@ -91,7 +97,7 @@ def write_image(path, img):
 
 def list_images(load_path):
     """The image files of a folder (sorted), or the one file given."""
-    exts = NATIVE_EXT + (PIL_EXT if _pil() is not None else ())
+    exts = NATIVE_EXT + (PIL_EXT if _pil() is not None else JPEG_EXT)
     if os.path.isfile(load_path):
         return os.path.dirname(load_path) or ".", [os.path.basename(load_path)]
     if not os.path.isdir(load_path):

@@ -62,7 +62,8 @@ class Trainer:
         self.current_step = 0                             # global step (epoch * max_iter + iter): schedule / TensorBoard axis
         self.run_steps = 0                                # steps of THIS run: what --steps limits
         os.makedirs(self.file_name, exist_ok=True)
-        if not args.synthetic:
+        check_data_args(args)
+        if not args.synthetic and not getattr(args, "data_dir", None):
             print("note: the COCO24P loader of the reference reads hard-coded paths (datasets/coco24p.py:19-20) and is out of "
                   "scope; the synthetic source with the same label layout is used (--synthetic)")
         # Round 5: the raw uint8 source is the DEFAULT (0.98 of bench.py against 0.91 for ready-made fp32 canvases from four loader
@@ -412,6 +413,24 @@ def weight_decay_arg(args, exp):
     return w
 
 
+def check_data_args(args):
+    """--data-dir / --label-dir: a folder of JPEG files and one of txt labels (datasets.COCO24PFolderDataset).  Its batches are raw
+    (images of any sizes, entropy-decoded in the loader processes, finished and letterboxed on the GPU behind the prefetcher)."""
+    data, label = getattr(args, "data_dir", None), getattr(args, "label_dir", None)
+    val_data, val_label = getattr(args, "val_data_dir", None), getattr(args, "val_label_dir", None)
+    if (data is None) != (label is None):
+        raise SystemExit("train_24p.py: --data-dir and --label-dir go together (images <stem>.jpg, labels <stem>.txt)")
+    if (val_data is None) != (val_label is None):
+        raise SystemExit("train_24p.py: --val-data-dir and --val-label-dir go together")
+    if data is None and val_data is None:
+        return
+    if args.synthetic:
+        raise SystemExit("train_24p.py: --data-dir / --val-data-dir read a real dataset; drop --synthetic")
+    if args.fp32_batches or args.no_prefetch:
+        raise SystemExit("train_24p.py: --data-dir / --val-data-dir batches are decoded and letterboxed on the GPU behind the prefetcher "
+                         "(drop --no-prefetch / --fp32-batches)")
+
+
 def check_mixup_args(args):
     """--mixup blends a second image into the mosaic images of --augment: it needs --augment."""
     if getattr(args, "mixup", False) and not args.augment:
@@ -473,7 +492,14 @@ def make_parser():
     p.add_argument("--num_machines", default=1, type=int, help="num of node for training")
     # additions of this build
     p.add_argument("--device", default="cuda", type=str, help="cuda or cuda:N (the ep24 path has no CPU fallback: cpu is refused)")
-    p.add_argument("--synthetic", action="store_true", help="synthetic images / labels with the reference's layout (the only source here)")
+    p.add_argument("--synthetic", action="store_true", help="synthetic images / labels with the reference's layout (the source when no --data-dir is given)")
+    p.add_argument("--data-dir", default=None, type=str, help="folder of training images <stem>.jpg (baseline JPEG; with --label-dir): "
+                   "datasets.COCO24PFolderDataset, Huffman stage in the loader processes, IDCT / upsampling / colour on the GPU (ep24.jpeg)")
+    p.add_argument("--label-dir", default=None, type=str, help="folder of COCO_24p_label/<stem>.txt files (labels_create_24p.py writes them)")
+    p.add_argument("--val-data-dir", default=None, type=str, help="folder of validation images (with --val-label-dir) for --eval-interval")
+    p.add_argument("--val-label-dir", default=None, type=str, help="folder of validation label files")
+    p.add_argument("--jpeg-decoder", default=None, choices=["gpu", "pil"], help="gpu (default): ep24.jpeg; pil: Pillow's decode in the loader "
+                   "processes, for files the native path refuses (progressive, CMYK, 12-bit)")
     p.add_argument("--output-dir", default=None, type=str, help="overrides exp.output_dir")
     p.add_argument("--synthetic-len", default=0, type=int, help="images per synthetic epoch (overrides exp.synthetic_len; a checkpoint is written per epoch)")
     p.add_argument("--steps", default=0, type=int, help="stop after this many steps (0 = run all epochs)")
@@ -538,6 +564,9 @@ def main(exp, args):
         exp.nms_iou_type = args.nms_iou
     if args.synthetic_len:
         exp.synthetic_len = args.synthetic_len
+    for name in ("data_dir", "label_dir", "val_data_dir", "val_label_dir", "jpeg_decoder"):
+        if getattr(args, name, None) is not None:
+            setattr(exp, name, getattr(args, name))
     trainer = Trainer(exp, args)
     trainer.train()
     return trainer

@@ -929,6 +929,27 @@ int ep24_resize_bilinear_f32(const float* src, int n, int sh, int sw, float* dst
  * multiply each: targets[..., 1::2] * scale_x, targets[..., 2::2] * scale_y).  out == in is allowed.  rows <= 2^40. */
 int ep24_scale_labels(const float* in, float* out, int64_t rows, float scale_x, float scale_y, void* stream);
 
+/* Baseline JPEG decode, the arithmetic half ("JPEG decode"): what libjpeg's default path computes behind its Huffman stage
+ * - dequantisation, the islow integer IDCT, "fancy" chroma upsampling, 16-bit fixed-point YCbCr -> RGB, clamp - bit for bit, for a
+ * batch of images of any sizes and samplings in two launches.  The Huffman stage is libep24jpeg.so (include/ep24_jpeg.h), on the host.
+ * ep24_jpeg_idct: coef = the int16 coefficient blocks of all planes (a plane = one component of one image), 64 per block in natural
+ *   order, plane after plane, block row-major within a plane over its MCU-padded grid; qt = nqt tables of 64 uint16, natural order
+ *   (both 16-byte aligned); plane_desc[n_planes + 1][4] int64 = {first block of the plane (cumulative, plane 0: 0), blocks per row,
+ *   index of its table, 0}, row n_planes = {total_blocks}.  planes (8-byte aligned, 64 * total_blocks bytes): plane p is the uint8
+ *   raster of 8 * blocks-per-row samples per row at byte 64 * first block.  One launch for every block of every image.
+ * ep24_jpeg_color: image_desc[n + 1][12] int64 = {0 first 4-pixel group of the image (cumulative, image 0: 0; an image has
+ *   ceil(H * W / 4)), 1 byte offset of the image in out (a multiple of 4), 2 H, 3 W, 4 mode (0 one component, 1 4:4:4, 2 4:2:2 = h2v1,
+ *   3 4:2:0 = h2v2), 5 byte offset of the Y plane in planes, 6 its row stride, 7 / 8 byte offsets of the Cb / Cr planes, 9 their row
+ *   stride, 10 dw = ceil(W / 2) (W for mode 1), 11 dh = ceil(H / 2) for mode 3, else H}, row n = {total_groups}.  out: every image a
+ *   contiguous uint8 [H, W, 3] (the form ep24_preproc_u8 reads), channels B, G, R with bgr != 0, else R, G, B; a one-component image
+ *   gives three equal channels.  One launch.
+ * No image index sits in a grid dimension.  A store that a descriptor would send outside planes / out is dropped.  EP24_E_ARG: a
+ * negative count, a null pointer with work to do, a misaligned buffer; a count of 0 launches nothing. */
+int ep24_jpeg_idct(const void* coef, const void* qt, int nqt, const int64_t* plane_desc, int n_planes, int64_t total_blocks,
+                   uint8_t* planes, void* stream);
+int ep24_jpeg_color(const uint8_t* planes, const int64_t* image_desc, int n, int64_t total_groups, uint8_t* out, int64_t out_bytes,
+                    int bgr, void* stream);
+
 /* Training augmentation (mosaic, random affine, mixup, mirror, HSV), two launches per batch.  Every output image
  * is assembled from up to four TILES: a tile is one source image, resized by s = min(S_h/h, S_w/w) as preproc resizes it and
  * placed on a canvas (2 S_h x 2 S_w with four tiles for a mosaic; S_h x S_w with one tile at the top left without).  Shared inputs:
