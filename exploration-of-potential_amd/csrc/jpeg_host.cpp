@@ -3,6 +3,9 @@
 //
 // Every read of the file goes through a position that is checked against n; every write goes to coef_out below ncoef (<= capacity)
 // or into the header; a block decodes in at most 64 steps whatever the bits say, so corrupt input ends in EP24JPEG_E_DATA.
+//
+// The writer (ep24jpeg_entropy_encode, below the decoder's helpers) is its mirror: markers, the Annex K Huffman tables and the
+// interleaved scan from a header and coefficients in the decoder's layout.  Every byte goes through put_byte, which checks the capacity.
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
@@ -270,7 +273,285 @@ inline int receive_extend(Bits& b, int s) {
     return v + (below & (1 - (1 << s)));
 }
 
+// ---- the encoder's side: Annex K's tables, a bit writer that never leaves its buffer ----
+
+const uint8_t kBaseQ[2][64] = {
+    {16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
+     18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99},
+    {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99,
+     99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99}};
+
+// the typical Huffman tables of Annex K.3: code counts per length 1 .. 16, then the symbols; [0] luminance, [1] chrominance
+const uint8_t kDcBits[2][16] = {{0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0}, {0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0}};
+const uint8_t kDcVals[12] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11};
+const uint8_t kAcBits[2][16] = {{0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 125}, {0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 119}};
+const uint8_t kAcVals[2][162] = {
+    {0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61, 0x07, 0x22, 0x71, 0x14, 0x32, 0x81, 0x91, 0xa1,
+     0x08, 0x23, 0x42, 0xb1, 0xc1, 0x15, 0x52, 0xd1, 0xf0, 0x24, 0x33, 0x62, 0x72, 0x82, 0x09, 0x0a, 0x16, 0x17, 0x18, 0x19, 0x1a, 0x25, 0x26,
+     0x27, 0x28, 0x29, 0x2a, 0x34, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56,
+     0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x83, 0x84, 0x85,
+     0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa,
+     0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6,
+     0xd7, 0xd8, 0xd9, 0xda, 0xe1, 0xe2, 0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf1, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9,
+     0xfa},
+    {0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07, 0x61, 0x71, 0x13, 0x22, 0x32, 0x81, 0x08, 0x14, 0x42,
+     0x91, 0xa1, 0xb1, 0xc1, 0x09, 0x23, 0x33, 0x52, 0xf0, 0x15, 0x62, 0x72, 0xd1, 0x0a, 0x16, 0x24, 0x34, 0xe1, 0x25, 0xf1, 0x17, 0x18, 0x19,
+     0x1a, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4a, 0x53, 0x54, 0x55,
+     0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x82, 0x83,
+     0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8,
+     0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4,
+     0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe2, 0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9,
+     0xfa}};
+
+struct EncHuff {
+    uint16_t code[256];
+    uint8_t len[256];
+};
+
+void build_enc(EncHuff& e, const uint8_t* bits, const uint8_t* vals) {
+    memset(&e, 0, sizeof(e));
+    unsigned code = 0;
+    int k = 0;
+    for (int l = 1; l <= 16; ++l) {
+        for (int i = 0; i < bits[l - 1]; ++i, ++k) {
+            e.code[vals[k]] = (uint16_t)code++;
+            e.len[vals[k]] = (uint8_t)l;
+        }
+        code <<= 1;
+    }
+}
+
+// what ep24.jpeg._check refuses, and what the marker segments cannot say
+int check_header(const ep24jpeg_header& h, int& mcus_x, int& mcus_y) {
+    mcus_x = mcus_y = 0;
+    if ((h.ncomp != 1 && h.ncomp != 3) || h.width < 1 || h.height < 1 || h.width > EP24JPEG_MAX_SIDE || h.height > EP24JPEG_MAX_SIDE)
+        return fail(EP24JPEG_E_ARG, "jpeg encode: inconsistent header (%d components, %d x %d)", h.ncomp, h.width, h.height);
+    if (h.restart_interval < 0 || h.restart_interval > 65535)
+        return fail(EP24JPEG_E_ARG, "jpeg encode: restart interval %d outside 0 .. 65535", h.restart_interval);
+    if (h.ncomp == 1) {
+        if (h.h[0] != 1 || h.v[0] != 1) return fail(EP24JPEG_E_ARG, "jpeg encode: a one-component image is sampled 1x1");
+    } else {
+        const bool luma = (h.h[0] == 1 && h.v[0] == 1) || (h.h[0] == 2 && h.v[0] == 1) || (h.h[0] == 2 && h.v[0] == 2);
+        if (!luma || h.h[1] != 1 || h.v[1] != 1 || h.h[2] != 1 || h.v[2] != 1)
+            return fail(EP24JPEG_E_ARG, "jpeg encode: sampling %dx%d,%dx%d,%dx%d (luma 1x1, 2x1 or 2x2 with chroma 1x1)", h.h[0], h.v[0], h.h[1],
+                        h.v[1], h.h[2], h.v[2]);
+    }
+    mcus_x = (h.width + 8 * h.h[0] - 1) / (8 * h.h[0]);
+    mcus_y = (h.height + 8 * h.v[0] - 1) / (8 * h.v[0]);
+    int64_t ncoef = 0;
+    for (int c = 0; c < h.ncomp; ++c) {
+        if (h.blocks_w[c] != mcus_x * h.h[c] || h.blocks_h[c] != mcus_y * h.v[c] || h.nblocks[c] != (int64_t)h.blocks_w[c] * h.blocks_h[c])
+            return fail(EP24JPEG_E_ARG, "jpeg encode: the block grid of component %d does not fit a %d x %d image", c, h.width, h.height);
+        ncoef += 64 * h.nblocks[c];
+        for (int k = 0; k < 64; ++k)
+            if (h.qt[c][k] < 1 || h.qt[c][k] > 255)
+                return fail(EP24JPEG_E_ARG, "jpeg encode: quantisation table entry %d of component %d is %d (baseline: 1 .. 255)", k, c, h.qt[c][k]);
+    }
+    if (h.ncoef != ncoef) return fail(EP24JPEG_E_ARG, "jpeg encode: ncoef %lld is not 64 x the %lld blocks", (long long)h.ncoef, (long long)(ncoef / 64));
+    return EP24JPEG_OK;
+}
+
+int64_t encode_bound(const ep24jpeg_header& h, int mcus_x, int mcus_y) {
+    // markers and tables stay below 1 KiB; a coefficient is at most a 16-bit code and 11 value bits, every byte of them stuffed: below
+    // 8 bytes; a restart marker and the padding in front of it: 4 bytes per MCU at the most
+    return 1024 + 8 * h.ncoef + 4 * (int64_t)mcus_x * mcus_y;
+}
+
+struct Writer {
+    uint8_t* out;
+    int64_t p, cap;
+    uint64_t acc;
+    int n;          // bits held in acc (below 32 between calls)
+};
+
+inline void put_byte(Writer& w, unsigned b) {
+    if (w.p < w.cap) w.out[w.p] = (uint8_t)b;
+    ++w.p;
+}
+
+inline void put_u16(Writer& w, unsigned v) {
+    put_byte(w, v >> 8);
+    put_byte(w, v & 255);
+}
+
+inline void put_bits(Writer& w, unsigned code, int len) {      // len <= 27
+    w.acc = (w.acc << len) | code;
+    w.n += len;
+    while (w.n >= 8) {
+        const unsigned b = (unsigned)(w.acc >> (w.n - 8)) & 255u;
+        put_byte(w, b);
+        if (b == 0xFF) put_byte(w, 0);
+        w.n -= 8;
+    }
+}
+
+inline void flush_bits(Writer& w) {                              // the last byte in front of a marker is filled with ones
+    if (w.n > 0) put_bits(w, (1u << (8 - w.n)) - 1, 8 - w.n);
+    w.acc = 0;
+    w.n = 0;
+}
+
+inline int bit_size(int a) { return a ? 32 - __builtin_clz((unsigned)a) : 0; }
+
+void put_dht(Writer& w, int tc_th, const uint8_t* bits, const uint8_t* vals) {
+    int cnt = 0;
+    for (int i = 0; i < 16; ++i) cnt += bits[i];
+    put_u16(w, 0xFFC4);
+    put_u16(w, 2 + 1 + 16 + cnt);
+    put_byte(w, (unsigned)tc_th);
+    for (int i = 0; i < 16; ++i) put_byte(w, bits[i]);
+    for (int i = 0; i < cnt; ++i) put_byte(w, vals[i]);
+}
+
 }  // namespace
+
+extern "C" int ep24jpeg_quality_tables(int quality, uint16_t qt[2][64]) {
+    if (!qt) return fail(EP24JPEG_E_ARG, "ep24jpeg_quality_tables: null pointer");
+    if (quality < 1 || quality > 100) return fail(EP24JPEG_E_ARG, "ep24jpeg_quality_tables: quality %d outside 1 .. 100", quality);
+    const int scale = quality < 50 ? 5000 / quality : 200 - 2 * quality;
+    for (int t = 0; t < 2; ++t)
+        for (int k = 0; k < 64; ++k) {
+            int v = (kBaseQ[t][k] * scale + 50) / 100;
+            qt[t][k] = (uint16_t)(v < 1 ? 1 : v > 255 ? 255 : v);
+        }
+    return EP24JPEG_OK;
+}
+
+extern "C" int64_t ep24jpeg_encode_bound(const ep24jpeg_header* header) {
+    if (!header) return fail(EP24JPEG_E_ARG, "ep24jpeg_encode_bound: null pointer");
+    int mx, my;
+    const int rc = check_header(*header, mx, my);
+    if (rc) return rc;
+    return encode_bound(*header, mx, my);
+}
+
+extern "C" int ep24jpeg_entropy_encode(const ep24jpeg_header* header, const int16_t* coef, int64_t ncoef, uint8_t* out, int64_t capacity,
+                                       int64_t* nbytes) {
+    if (!header || !coef || !out || !nbytes) return fail(EP24JPEG_E_ARG, "ep24jpeg_entropy_encode: null pointer");
+    const ep24jpeg_header& h = *header;
+    int mcus_x, mcus_y;
+    int rc = check_header(h, mcus_x, mcus_y);
+    if (rc) return rc;
+    if (ncoef != h.ncoef) return fail(EP24JPEG_E_ARG, "ep24jpeg_entropy_encode: %lld coefficients given, the header holds %lld", (long long)ncoef, (long long)h.ncoef);
+    const int64_t bound = encode_bound(h, mcus_x, mcus_y);
+    if (capacity < bound) return fail(EP24JPEG_E_ARG, "ep24jpeg_entropy_encode: capacity %lld below the bound %lld", (long long)capacity, (long long)bound);
+
+    Writer w = {out, 0, capacity, 0, 0};
+    put_u16(w, 0xFFD8);
+    static const uint8_t kApp0[16] = {0x00, 0x10, 'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0};
+    put_u16(w, 0xFFE0);
+    for (int i = 0; i < 16; ++i) put_byte(w, kApp0[i]);
+    // Cb and Cr share table 1 when their tables are equal (what every common encoder writes); a third table otherwise
+    int tq[3] = {0, 1, 1}, ntab = h.ncomp == 1 ? 1 : 2;
+    if (h.ncomp == 3 && memcmp(h.qt[1], h.qt[2], sizeof(h.qt[1])) != 0) tq[2] = 2, ntab = 3;
+    for (int t = 0; t < ntab; ++t) {
+        put_u16(w, 0xFFDB);
+        put_u16(w, 67);
+        put_byte(w, (unsigned)t);
+        for (int k = 0; k < 64; ++k) put_byte(w, h.qt[t][kZigzag[k]]);
+    }
+    put_u16(w, 0xFFC0);
+    put_u16(w, 8 + 3 * h.ncomp);
+    put_byte(w, 8);
+    put_u16(w, (unsigned)h.height);
+    put_u16(w, (unsigned)h.width);
+    put_byte(w, (unsigned)h.ncomp);
+    for (int c = 0; c < h.ncomp; ++c) {
+        put_byte(w, (unsigned)(c + 1));
+        put_byte(w, (unsigned)((h.h[c] << 4) | h.v[c]));
+        put_byte(w, (unsigned)tq[c]);
+    }
+    const int nh = h.ncomp == 1 ? 1 : 2;
+    for (int t = 0; t < nh; ++t) {
+        put_dht(w, 0x00 | t, kDcBits[t], kDcVals);
+        put_dht(w, 0x10 | t, kAcBits[t], kAcVals[t]);
+    }
+    if (h.restart_interval > 0) {
+        put_u16(w, 0xFFDD);
+        put_u16(w, 4);
+        put_u16(w, (unsigned)h.restart_interval);
+    }
+    put_u16(w, 0xFFDA);
+    put_u16(w, 6 + 2 * h.ncomp);
+    put_byte(w, (unsigned)h.ncomp);
+    for (int c = 0; c < h.ncomp; ++c) {
+        put_byte(w, (unsigned)(c + 1));
+        put_byte(w, c ? 0x11u : 0x00u);
+    }
+    put_byte(w, 0);
+    put_byte(w, 63);
+    put_byte(w, 0);
+
+    EncHuff dc[2], ac[2];
+    for (int t = 0; t < 2; ++t) {
+        build_enc(dc[t], kDcBits[t], kDcVals);
+        build_enc(ac[t], kAcBits[t], kAcVals[t]);
+    }
+    const int16_t* base[3];
+    int64_t off = 0;
+    for (int c = 0; c < h.ncomp; ++c) {
+        base[c] = coef + off;
+        off += 64 * h.nblocks[c];
+    }
+    int pred[3] = {0, 0, 0};
+    const int ri = h.restart_interval;
+    int rst = 0, left = ri;
+    for (int my = 0; my < mcus_y; ++my)
+        for (int mx = 0; mx < mcus_x; ++mx) {
+            if (ri) {
+                if (left == 0) {
+                    flush_bits(w);
+                    put_u16(w, 0xFFD0u + (unsigned)rst);
+                    rst = (rst + 1) & 7;
+                    pred[0] = pred[1] = pred[2] = 0;
+                    left = ri;
+                }
+                --left;
+            }
+            for (int c = 0; c < h.ncomp; ++c) {
+                const EncHuff& hdc = dc[c ? 1 : 0];
+                const EncHuff& hac = ac[c ? 1 : 0];
+                for (int by = 0; by < h.v[c]; ++by)
+                    for (int bx = 0; bx < h.h[c]; ++bx) {
+                        const int16_t* blk = base[c] + ((int64_t)(my * h.v[c] + by) * h.blocks_w[c] + (mx * h.h[c] + bx)) * 64;
+                        const int diff = blk[0] - pred[c];
+                        pred[c] = blk[0];
+                        if (diff < -2047 || diff > 2047)
+                            return fail(EP24JPEG_E_ARG, "jpeg encode: DC difference %d in MCU %d is outside baseline's +-2047", diff, my * mcus_x + mx);
+                        int a = diff < 0 ? -diff : diff;
+                        int s = bit_size(a);
+                        put_bits(w, hdc.code[s], hdc.len[s]);
+                        if (s) put_bits(w, (unsigned)(diff < 0 ? diff - 1 : diff) & ((1u << s) - 1), s);
+                        int run = 0;
+                        for (int k = 1; k < 64; ++k) {
+                            const int v = blk[kZigzag[k]];
+                            if (v == 0) {
+                                ++run;
+                                continue;
+                            }
+                            if (v < -1023 || v > 1023)
+                                return fail(EP24JPEG_E_ARG, "jpeg encode: AC coefficient %d in MCU %d is outside baseline's +-1023", v, my * mcus_x + mx);
+                            while (run > 15) {
+                                put_bits(w, hac.code[0xF0], hac.len[0xF0]);
+                                run -= 16;
+                            }
+                            a = v < 0 ? -v : v;
+                            s = bit_size(a);
+                            const int sym = (run << 4) | s;
+                            put_bits(w, hac.code[sym], hac.len[sym]);
+                            put_bits(w, (unsigned)(v < 0 ? v - 1 : v) & ((1u << s) - 1), s);
+                            run = 0;
+                        }
+                        if (run) put_bits(w, hac.code[0], hac.len[0]);
+                    }
+            }
+        }
+    flush_bits(w);
+    put_u16(w, 0xFFD9);
+    if (w.p > capacity) return fail(EP24JPEG_E_ARG, "ep24jpeg_entropy_encode: the stream outgrew its bound (%lld > %lld)", (long long)w.p, (long long)capacity);
+    *nbytes = w.p;
+    return EP24JPEG_OK;
+}
 
 extern "C" int ep24jpeg_abi_version(void) { return EP24JPEG_ABI_VERSION; }
 extern "C" const char* ep24jpeg_last_error(void) { return g_err; }

@@ -1,4 +1,4 @@
-"""Baseline JPEG decode, split between host and GPU ("JPEG decode").
+"""Baseline JPEG decode and encode, split between host and GPU ("JPEG decode" and "JPEG encode").
 
     coefs = entropy_decode(bytes)          # host: libep24jpeg.so (marker parser + Huffman), no GPU, no torch.cuda - loader processes
     images = finish([coefs, ...])          # GPU: one upload, ep24_jpeg_idct + ep24_jpeg_color on the current stream, no host sync
@@ -8,6 +8,17 @@ The result is what libjpeg's default path (Pillow, ``cv2.imread``) gives, bit fo
 default (``cv2.imread``'s order, what ``ep24.input.preproc_batch`` is fed), RGB with ``bgr=False``.  Progressive, arithmetic-coded,
 12-bit and four-component files, other samplings than 4:4:4 / 4:2:2 / 4:2:0, several scans and sides above 8192 raise ``JpegError``
 with ``code == EP24_E_UNSUPPORTED``; corrupt files raise it with ``EP24JPEG_E_DATA``.
+
+The writer mirrors the reader:
+
+    coefs = forward([image, ...])          # GPU: one descriptor upload, ep24_jpeg_sample + ep24_jpeg_fdct, one copy to the host
+    data = entropy_encode(coefs[i])        # host: libep24jpeg.so (markers, Annex K Huffman tables, the scan), no GPU
+    datas = encode([image, ...])           # both
+
+The files are what libjpeg-turbo's default compress path (Pillow, ``cv2.imwrite``) writes from the same pixels at the same quality
+and sampling, byte for byte: baseline, 4:4:4 / 4:2:2 / 4:2:0 or one component, quality 1 .. 100 or explicit tables, optional restart
+markers.  Input that is not uint8, not on the GPU or above 8192 a side raises ``JpegError``.  Optimised Huffman tables, progressive
+and arithmetic coding and 12-bit samples are out of scope.
 """
 import ctypes
 import os
@@ -108,6 +119,13 @@ def host_lib():
         L.ep24jpeg_parse.argtypes = [ctypes.c_char_p, ctypes.c_int64, ctypes.POINTER(_Header)]
         L.ep24jpeg_entropy_decode.restype = ctypes.c_int
         L.ep24jpeg_entropy_decode.argtypes = [ctypes.c_char_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64]
+        L.ep24jpeg_quality_tables.restype = ctypes.c_int
+        L.ep24jpeg_quality_tables.argtypes = [ctypes.c_int, ctypes.c_void_p]
+        L.ep24jpeg_encode_bound.restype = ctypes.c_int64
+        L.ep24jpeg_encode_bound.argtypes = [ctypes.POINTER(_Header)]
+        L.ep24jpeg_entropy_encode.restype = ctypes.c_int
+        L.ep24jpeg_entropy_encode.argtypes = [ctypes.POINTER(_Header), ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
+                                              ctypes.POINTER(ctypes.c_int64)]
         if L.ep24jpeg_abi_version() != ABI_VERSION:
             raise Ep24Error("ep24: %s reports ABI version %d, ep24.jpeg expects %d - rebuild the library" %
                             (HOST_LIB_PATH, L.ep24jpeg_abi_version(), ABI_VERSION))
@@ -268,6 +286,165 @@ def finish(items, device="cuda:0", bgr=True):
 def decode(datas, device="cuda:0", bgr=True):
     """list of JPEG files as bytes -> list of uint8 [h, w, 3] device tensors: ``entropy_decode`` of each, then one ``finish``."""
     return finish([entropy_decode(d) for d in datas], device=device, bgr=bgr)
+
+
+# ---- the writer ----
+
+SAMPLINGS = {"4:4:4": 1, "4:2:2": 2, "4:2:0": 3}
+_LUMA_FACTORS = {0: (1, 1), 1: (1, 1), 2: (2, 1), 3: (2, 2)}
+MAX_SIDE = 8192
+
+
+def quality_tables(q):
+    """``jpeg_set_quality``'s scaling of the Annex K tables for quality 1 .. 100 -> uint16 [2, 64] (luminance, chrominance), natural
+    order.  Host library only."""
+    L = host_lib()
+    qt = ((ctypes.c_uint16 * 64) * 2)()
+    rc = L.ep24jpeg_quality_tables(int(q), qt)
+    if rc:
+        _raise(L, rc)
+    return np.array([list(qt[0]), list(qt[1])], dtype=np.uint16)
+
+
+def _tables(quality):
+    """``quality`` as an int, or explicit tables [1 .. 3, 64] (natural order; the last row serves the components beyond it)."""
+    if isinstance(quality, (int, np.integer)):
+        return quality_tables(quality)
+    qt = np.asarray(quality)
+    if qt.ndim != 2 or qt.shape[1] != 64 or not 1 <= qt.shape[0] <= 3 or qt.dtype.kind not in "iu" or int(qt.min()) < 1 or int(qt.max()) > 255:
+        raise JpegError(EP24_E_ARG, "encode: quantisation tables must be integers 1 .. 255 of shape [1 .. 3, 64]")
+    return qt.astype(np.uint16)
+
+
+def _grids(height, width, mode):
+    """Per component (h, v, wb, hb, blocks_w, blocks_h): sampling factors, the real block grid and the MCU-padded one."""
+    hmax, vmax = _LUMA_FACTORS[mode]
+    mx, my = -(-width // (8 * hmax)), -(-height // (8 * vmax))
+    out = []
+    for c in range(1 if mode == 0 else 3):
+        hc, vc = (hmax, vmax) if c == 0 else (1, 1)
+        cw, ch = -(-width * hc // hmax), -(-height * vc // vmax)
+        out.append((hc, vc, -(-cw // 8), -(-ch // 8), mx * hc, my * vc))
+    return out
+
+
+def make_header(height, width, mode, qt, restart_interval=0):
+    """-> JpegHeader of an image to be written: mode 0 one component, 1 4:4:4, 2 4:2:2, 3 4:2:0; qt [1 .. 3, 64] natural order."""
+    c = _Header()
+    gr = _grids(height, width, mode)
+    c.width, c.height, c.ncomp, c.restart_interval, c.ncoef = width, height, len(gr), restart_interval, 0
+    for i, (hc, vc, _, _, bw, bh) in enumerate(gr):
+        c.h[i], c.v[i], c.blocks_w[i], c.blocks_h[i], c.nblocks[i] = hc, vc, bw, bh, bw * bh
+        c.ncoef += 64 * bw * bh
+        for k, v in enumerate(qt[min(i, len(qt) - 1)]):
+            c.qt[i][k] = int(v)
+    return JpegHeader(c)
+
+
+def _c_header(hd):
+    c = _Header()
+    n = int(hd.ncomp)
+    if n not in (1, 3) or any(len(x) != n for x in (hd.h, hd.v, hd.blocks_w, hd.blocks_h, hd.nblocks)) or np.asarray(hd.qt).shape != (n, 64):
+        raise JpegError(EP24_E_ARG, "entropy_encode: inconsistent header (%d components)" % n)
+    c.width, c.height, c.ncomp, c.restart_interval, c.ncoef = int(hd.width), int(hd.height), n, int(hd.restart_interval), int(hd.ncoef)
+    for i in range(n):
+        c.h[i], c.v[i], c.blocks_w[i], c.blocks_h[i], c.nblocks[i] = hd.h[i], hd.v[i], hd.blocks_w[i], hd.blocks_h[i], hd.nblocks[i]
+        for k in range(64):
+            c.qt[i][k] = int(hd.qt[i][k])
+    return c
+
+
+def entropy_encode(coefficients):
+    """JpegCoefficients -> the bytes of a baseline JFIF file: the host half of the writer (markers, the Annex K Huffman tables, the
+    interleaved scan with restart markers every ``header.restart_interval`` MCUs).  Uses the host library only."""
+    L, hd = host_lib(), coefficients.header
+    coef = coefficients.coef
+    if not isinstance(coef, np.ndarray) or coef.dtype != np.int16 or coef.ndim != 1:
+        raise JpegError(EP24_E_ARG, "entropy_encode: the coefficients must be a one-dimensional int16 array")
+    coef = np.ascontiguousarray(coef)
+    c = _c_header(hd)
+    bound = L.ep24jpeg_encode_bound(ctypes.byref(c))
+    if bound < 0:
+        _raise(L, bound)
+    out = np.empty(bound, dtype=np.uint8)                  # untouched pages of it cost nothing
+    n = ctypes.c_int64(0)
+    rc = L.ep24jpeg_entropy_encode(ctypes.byref(c), coef.ctypes.data, coef.size, out.ctypes.data, out.size, ctypes.byref(n))
+    if rc:
+        _raise(L, rc)
+    return out[:n.value].tobytes()
+
+
+def forward(images, quality=95, subsampling="4:2:0", bgr=True, restart_interval=0):
+    """The GPU half of the writer.  images: uint8 device tensors ``[h, w, 3]`` (BGR by default, as ``decode`` gives them; RGB with
+    ``bgr=False``), or ``[h, w]`` / ``[h, w, 1]`` for a one-component file; any sizes up to 8192 a side.  -> list of JpegCoefficients
+    whose coefficients equal libjpeg's at these tables.  ``quality``: 1 .. 100, or explicit tables (``_tables``).  One descriptor
+    upload, ep24_jpeg_sample + ep24_jpeg_fdct on the current stream, one device-to-host copy.  The pixels are read where they lie:
+    a view with a row stride (a crop of a wider tensor) is not copied first (only a tensor whose pixels are not packed is)."""
+    from . import _lib
+    images = list(images)
+    qt = _tables(quality)
+    if subsampling not in SAMPLINGS:
+        raise JpegError(EP24_E_ARG, "encode: subsampling %r (one of %s)" % (subsampling, ", ".join(sorted(SAMPLINGS))))
+    if not 0 <= int(restart_interval) <= 65535:
+        raise JpegError(EP24_E_ARG, "encode: restart interval %r outside 0 .. 65535" % (restart_interval,))
+    if not images:
+        return []
+    import torch
+    srcs = []
+    for i, im in enumerate(images):
+        if not isinstance(im, torch.Tensor) or im.dtype != torch.uint8:
+            raise JpegError(EP24_E_ARG, "encode: image %d is not a uint8 tensor (got %s)" % (i, getattr(im, "dtype", type(im).__name__)))
+        if not im.is_cuda:
+            raise JpegError(EP24_E_ARG, "encode: image %d is not on the GPU (the arithmetic runs only as HIP kernels)" % i)
+        if im.ndim not in (2, 3) or (im.ndim == 3 and im.shape[2] not in (1, 3)) or im.device != images[0].device:
+            raise JpegError(EP24_E_ARG, "encode: image %d must be [h, w, 3], [h, w, 1] or [h, w] on one device (got %s)" % (i, tuple(im.shape)))
+        h, w = int(im.shape[0]), int(im.shape[1])
+        if not (1 <= h <= MAX_SIDE and 1 <= w <= MAX_SIDE):
+            raise JpegError(EP24_E_UNSUPPORTED, "encode: image %d is %d x %d: a side must be 1 .. %d" % (i, h, w, MAX_SIDE))
+        ch = 1 if im.ndim == 2 else int(im.shape[2])
+        packed = (w == 1 or im.stride(1) == ch) and (ch == 1 or im.stride(2) == 1)
+        srcs.append((im if packed else im.contiguous(), h, w, 0 if ch == 1 else SAMPLINGS[subsampling]))
+    _lib.require_gpu()
+    dev = images[0].device
+    idesc, pdesc, headers = [], [], []
+    groups = blocks = plane_off = 0
+    for im, h, w, mode in srcs:
+        gr = _grids(h, w, mode)
+        idesc.append([groups, im.data_ptr(), im.stride(0) if h > 1 else 0, h, w, mode + (256 if bgr and mode else 0), plane_off, 0])
+        for c, (hc, _, wb, hb, bw, bh) in enumerate(gr):
+            pdesc.append([blocks, bw, min(c, len(qt) - 1), plane_off, wb, hb, hc, 0])
+            blocks += bw * bh
+            plane_off += 64 * wb * hb
+        groups += 8 * gr[0][2] * gr[0][3] + (8 * gr[1][2] * gr[1][3] if mode else 0)
+        headers.append(make_header(h, w, mode, qt, int(restart_interval)))
+    idesc.append([groups] + [0] * 7)
+    pdesc.append([blocks] + [0] * 7)
+    idn, pdn = np.asarray(idesc, dtype=np.int64).reshape(-1), np.asarray(pdesc, dtype=np.int64).reshape(-1)
+    o_id = _al(qt.nbytes, 16)
+    o_pd = o_id + idn.nbytes
+    host = np.zeros(o_pd + pdn.nbytes, dtype=np.uint8)
+    host[:qt.nbytes] = np.ascontiguousarray(qt).view(np.uint8).reshape(-1)
+    host[o_id:o_pd] = idn.view(np.uint8)
+    host[o_pd:] = pdn.view(np.uint8)
+    with torch.cuda.device(dev):
+        buf = torch.from_numpy(host).to(dev, non_blocking=True)
+        planes = torch.empty(plane_off, dtype=torch.uint8, device=dev)
+        coef = torch.empty(blocks * 64, dtype=torch.int16, device=dev)
+        base, s = buf.data_ptr(), _lib.stream_ptr()
+        _lib.call("jpeg_sample", base + o_id, len(srcs), groups, _lib.ptr(planes), plane_off, s)
+        _lib.call("jpeg_fdct", _lib.ptr(planes), plane_off, base, len(qt), base + o_pd, len(pdesc) - 1, blocks, _lib.ptr(coef), s)
+        flat = coef.cpu().numpy()                          # waits for the stream: srcs (and any packed copies) outlive the kernels
+    out, p = [], 0
+    for hd in headers:
+        out.append(JpegCoefficients(hd, flat[p:p + hd.ncoef]))
+        p += hd.ncoef
+    return out
+
+
+def encode(images, quality=95, subsampling="4:2:0", bgr=True, restart_interval=0):
+    """list of uint8 device images -> list of JPEG files as bytes: one ``forward``, then ``entropy_encode`` of each.  The default is
+    what ``cv2.imwrite`` writes: quality 95 at 4:2:0, BGR input."""
+    return [entropy_encode(c) for c in forward(images, quality, subsampling, bgr, restart_interval)]
 
 
 def is_coefficients(x):

@@ -10,7 +10,9 @@ save every image with its 24-point detections drawn on it.
 ``save_eval_results`` / ``vis`` (:266-367) without the host-side OpenCV.  Results go to ``<output_dir>/<timestamp>/``: the drawn
 image under its own name, ``<name>.dets.npy`` with the ``[n, 29]`` float32 rows beside it, and one ``detections.json`` (file, size,
 ratio, count).  ``--save-segm FILE`` also writes every detection of the run as a COCO "segm" result (``ep24.results``: the polygon
-rasterised on the original image and run-length encoded on the GPU).  ``.npy`` (uint8 HWC) and binary PPM are read and written natively; JPEG / PNG when PIL is installed (without it, baseline JPEG files are read through ``ep24.jpeg``).
+rasterised on the original image and run-length encoded on the GPU).  ``.npy`` (uint8 HWC) and binary PPM are read and written natively; JPEG / PNG / BMP through PIL when it is installed.  Without it
+baseline JPEG files are read AND written through ``ep24.jpeg`` (``--jpeg-encoder``, ``--jpeg-quality``; the drawn device tensors of a
+batch are encoded in one call), and a ``.png`` / ``.bmp`` name ends in a clear message.
 """
 import argparse
 import json
@@ -85,14 +87,48 @@ def read_image(path):
     return np.ascontiguousarray(img)
 
 
-def write_image(path, img):
-    ext = os.path.splitext(path)[1].lower()
-    if ext == ".npy":
-        np.save(path, img)
-    elif ext == ".ppm":
-        write_ppm(path, img)
-    else:
-        _pil().fromarray(img).save(path)
+def resolve_jpeg_encoder(choice):
+    """--jpeg-encoder: ``auto`` is PIL where it is installed and the project's own encoder (``ep24.jpeg``) otherwise."""
+    if choice == "auto":
+        return "pil" if _pil() is not None else "native"
+    if choice == "pil" and _pil() is None:
+        raise SystemExit("show_24p.py: --jpeg-encoder pil needs PIL, which is not installed (native writes baseline .jpg without it)")
+    return choice
+
+
+def write_images(paths, images, jpeg_encoder="auto", jpeg_quality=None):
+    """Saves a batch: uint8 [h, w, 3] RGB numpy arrays or (device) tensors.  ``.jpg`` / ``.jpeg`` names go through ``ep24.jpeg.encode``
+    with the native encoder - every one of the batch in one call, straight from the device tensors, at quality 95 and 4:2:0 (what
+    ``cv2.imwrite`` writes) unless ``jpeg_quality`` says otherwise - and through PIL with the other (its own defaults unless
+    ``jpeg_quality`` is given)."""
+    native = []
+    for path, img in zip(paths, images):
+        ext = os.path.splitext(path)[1].lower()
+        if ext in JPEG_EXT and resolve_jpeg_encoder(jpeg_encoder) == "native":
+            native.append((path, img if torch.is_tensor(img) else torch.from_numpy(np.ascontiguousarray(img))))
+            continue
+        arr = img.cpu().numpy() if torch.is_tensor(img) else img
+        if ext == ".npy":
+            np.save(path, arr)
+        elif ext == ".ppm":
+            write_ppm(path, arr)
+        else:
+            Image = _pil()
+            if Image is None:
+                raise SystemExit("show_24p.py: writing %s needs PIL, which is not installed (.npy, .ppm and .jpg are written natively)" % path)
+            kw = {"quality": int(jpeg_quality)} if ext in JPEG_EXT and jpeg_quality is not None else {}
+            Image.fromarray(arr).save(path, **kw)
+    if native:
+        from ep24 import jpeg
+        tensors = [t if t.is_cuda else t.cuda() for _, t in native]
+        datas = jpeg.encode(tensors, quality=95 if jpeg_quality is None else int(jpeg_quality), subsampling="4:2:0", bgr=False)
+        for (path, _), data in zip(native, datas):
+            with open(path, "wb") as fh:
+                fh.write(data)
+
+
+def write_image(path, img, jpeg_encoder="auto", jpeg_quality=None):
+    write_images([path], [img], jpeg_encoder, jpeg_quality)
 
 
 def list_images(load_path):
@@ -159,11 +195,12 @@ class Evaluator:
             images, ratios = preproc_batch(originals, self.input_size, device=self.device)
             outputs = postprocess(model(images, train=False), self.num_classes, conf_thre=args.conf, nms_thre=args.nms,
                                   nms_iou=args.nms_iou)
+            drawn_batch = []
             for name, img, ratio, dets in zip(names, originals, ratios, outputs):
                 drawn = draw_detections(img, dets, ratio=ratio, conf=args.draw_conf, num_classes=self.num_classes,
                                         class_names=self.class_names, fill_alpha=args.fill_alpha, show_scores=args.show_scores)
                 rows = np.zeros((0, 29), dtype=np.float32) if dets is None else dets.float().cpu().numpy()
-                write_image(os.path.join(self.save_folder, name), drawn.cpu().numpy())
+                drawn_batch.append(drawn)
                 np.save(os.path.join(self.save_folder, name + ".dets.npy"), rows)
                 records.append({"file": name, "height": int(img.shape[0]), "width": int(img.shape[1]), "ratio": float(ratio),
                                 "count": int(rows.shape[0])})
@@ -171,6 +208,7 @@ class Evaluator:
                     stem = os.path.splitext(name)[0]
                     segm.add(int(stem) if stem.isascii() and stem.isdigit() else stem, dets, ratio, (int(img.shape[0]), int(img.shape[1])))
                 print("%s: %d detections" % (name, rows.shape[0]))
+            write_images([os.path.join(self.save_folder, f) for f in names], drawn_batch, args.jpeg_encoder, args.jpeg_quality)
         with open(os.path.join(self.save_folder, "detections.json"), "w") as fh:
             json.dump({"input_size": list(self.input_size), "conf": args.conf, "nms": args.nms, "nms_iou": args.nms_iou,
                        "draw_conf": args.draw_conf, "images": records}, fh, indent=1)
@@ -203,6 +241,10 @@ def make_parser():
                    "its polygon on the original image, score, bbox, area) to this json file")
     p.add_argument("--segm-category-ids", default="index", choices=["coco", "index"], help="--save-segm: category_id is COCO's id of "
                    "the class (80 classes) or the class index")
+    p.add_argument("--jpeg-encoder", default="auto", choices=["auto", "native", "pil"], help="who writes .jpg results: PIL, or the "
+                   "project's own baseline encoder (ep24.jpeg: arithmetic on the GPU); auto = PIL where it is installed, native otherwise")
+    p.add_argument("--jpeg-quality", default=None, type=int, metavar="Q", help="quality 1..100 of .jpg results (native default: 95 at "
+                   "4:2:0, what cv2.imwrite writes; PIL keeps its own default when the flag is absent)")
     p.add_argument("--device", default="cuda", type=str, help="cuda or cuda:N (the ep24 path has no CPU fallback: cpu is refused)")
     return p
 

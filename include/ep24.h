@@ -950,6 +950,29 @@ int ep24_jpeg_idct(const void* coef, const void* qt, int nqt, const int64_t* pla
 int ep24_jpeg_color(const uint8_t* planes, const int64_t* image_desc, int n, int64_t total_groups, uint8_t* out, int64_t out_bytes,
                     int bgr, void* stream);
 
+/* Baseline JPEG encode, the arithmetic half ("JPEG encode"): what libjpeg's default compress path computes in front of its
+ * Huffman stage - 16-bit fixed-point RGB -> YCbCr, h2v1 / h2v2 chroma downsampling with its edge rules, the islow integer forward
+ * DCT, quantisation, the dummy blocks of the MCU padding - in every coefficient, for a batch of images of any sizes and samplings in two
+ * launches.  The Huffman stage is ep24jpeg_entropy_encode of libep24jpeg.so (include/ep24_jpeg.h), on the host.
+ * ep24_jpeg_sample: image_desc[n + 1][8] int64 = {0 first 8-sample group of the image (cumulative, image 0: 0), 1 device address of
+ *   pixel (0, 0), 2 row stride in bytes, 3 H, 4 W, 5 mode (0 one component, 1 4:4:4, 2 4:2:2, 3 4:2:0) + 256 if the pixels are BGR,
+ *   6 byte offset of the image's Y plane in planes (a multiple of 8), 7 0}, row n = {total_groups}.  The pixels are read where they
+ *   lie: uint8, 3 bytes per pixel (1 for mode 0), rows `stride` apart.  With wb = ceil(cw / 8), hb = ceil(ch / 8) of a component
+ *   (cw = W, ch = H for Y; halved and rounded up as the mode says for Cb / Cr) its plane is the uint8 raster of hb * 8 rows of wb * 8
+ *   samples over its REAL block grid; Cb follows Y, Cr follows Cb.  An image has 8 hb wb groups for Y and, but for mode 0, as many of
+ *   its chroma grid for Cb and Cr together.  One launch.
+ * ep24_jpeg_fdct: plane_desc[n_planes + 1][8] int64 = {0 first block of the plane (cumulative over the MCU-padded grids, plane 0: 0),
+ *   1 blocks per row of the padded grid, 2 index of its table, 3 byte offset of the plane in planes, 4 wb, 5 hb (the real grid),
+ *   6 blocks of this component per MCU row (h), 7 0}, row n_planes = {total_blocks}; qt = nqt tables of 64 uint16, natural order.
+ *   coef (int16, 64 * total_blocks) is filled in ep24_jpeg_idct's layout, dummy blocks included: zero but for the DC of the block to
+ *   the left (in a dummy block row: of the last block of the row above in the same MCU).  One launch for every block of every image.
+ * No image index sits in a grid dimension.  A store (and a read of planes) that a descriptor would send outside planes is dropped.
+ * EP24_E_ARG: a negative count, a null pointer with work to do, a misaligned buffer (coef and qt 16 bytes, planes and descriptors 8);
+ * a count of 0 launches nothing. */
+int ep24_jpeg_sample(const int64_t* image_desc, int n, int64_t total_groups, uint8_t* planes, int64_t plane_bytes, void* stream);
+int ep24_jpeg_fdct(const uint8_t* planes, int64_t plane_bytes, const void* qt, int nqt, const int64_t* plane_desc, int n_planes,
+                   int64_t total_blocks, void* coef, void* stream);
+
 /* Training augmentation (mosaic, random affine, mixup, mirror, HSV), two launches per batch.  Every output image
  * is assembled from up to four TILES: a tile is one source image, resized by s = min(S_h/h, S_w/w) as preproc resizes it and
  * placed on a canvas (2 S_h x 2 S_w with four tiles for a mosaic; S_h x S_w with one tile at the top left without).  Shared inputs:

@@ -1,4 +1,4 @@
-/* ep24 - host entropy stage of the JPEG decoder: libep24jpeg.so (csrc/jpeg_host.cpp).
+/* ep24 - host entropy stage of the JPEG decoder and encoder: libep24jpeg.so (csrc/jpeg_host.cpp).
  *
  * A second, host-only library: no HIP runtime, no device code.  Loader processes load it without opening the GPU (they never load
  * libep24.so).  It parses a baseline JPEG file and undoes its Huffman coding; everything arithmetic (dequantisation, IDCT, chroma
@@ -50,6 +50,26 @@ int ep24jpeg_parse(const uint8_t* bytes, int64_t n, ep24jpeg_header* header_out)
  * component over the MCU-padded grid, 64 int16 per block in natural order (de-zigzagged, DC prediction undone, not dequantised).
  * capacity (in int16) below ncoef is EP24JPEG_E_ARG.  On an error the contents of coef_out are unspecified (but in bounds). */
 int ep24jpeg_entropy_decode(const uint8_t* bytes, int64_t n, int16_t* coef_out, int64_t capacity);
+
+/* ---- the writer: the host half of the baseline encoder (the arithmetic is ep24_jpeg_sample / ep24_jpeg_fdct of libep24.so) ---- */
+
+/* jpeg_set_quality's scaling of the Annex K tables, natural order: qt[0] luminance, qt[1] chrominance.  quality 1 .. 100
+ * (scale = q < 50 ? 5000 / q : 200 - 2 q; entry = (base * scale + 50) / 100 clamped to 1 .. 255); anything else: EP24JPEG_E_ARG. */
+int ep24jpeg_quality_tables(int quality, uint16_t qt[2][64]);
+
+/* The capacity in bytes ep24jpeg_entropy_encode needs for this header whatever the coefficients are (negative: the header is refused). */
+int64_t ep24jpeg_encode_bound(const ep24jpeg_header* header);
+
+/* Writes a baseline JFIF file from a header as ep24jpeg_parse fills it and coefficients in ep24jpeg_entropy_decode's layout: SOI, APP0
+ * (JFIF 1.01, density 1 x 1 without a unit), one DQT segment per table in zig-zag order (one table for one component; two for three,
+ * Cb and Cr sharing table 1 - three when their tables differ), SOF0, the Annex K Huffman tables as separate DHT segments (DC0, AC0,
+ * DC1, AC1; two for one component), DRI when restart_interval > 0, SOS, the interleaved scan (DC prediction, run/size coding with ZRL
+ * and EOB, FF 00 stuffing, 1-padding of the last byte in front of every marker, RSTn with the predictors reset), EOI.  *nbytes: the
+ * file's length.  EP24JPEG_E_ARG: capacity below ep24jpeg_encode_bound, ncoef other than the header's, a header ep24jpeg_parse
+ * could not have made (component count, side, sampling, block grid), a table entry outside 1 .. 255, a restart interval outside
+ * 0 .. 65535, a DC difference outside +-2047 or an AC coefficient outside +-1023.  Nothing is written outside out[0, capacity). */
+int ep24jpeg_entropy_encode(const ep24jpeg_header* header, const int16_t* coef, int64_t ncoef, uint8_t* out, int64_t capacity,
+                            int64_t* nbytes);
 
 #ifdef __cplusplus
 }
