@@ -51,12 +51,13 @@ __global__ __launch_bounds__(256) void relu_fwd_kernel(bf16* y, long ld, long M,
         bf16x8* p = reinterpret_cast<bf16x8*>(y + m * ld + cg * 8);
         bf16x8 v = *p;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = (float)v[j] > 0.f ? v[j] : (bf16)0.f;
+        for (int j = 0; j < 8; ++j) v[j] = (float)v[j] < 0.f ? (bf16)0.f : v[j];      // ATen's relu: NaN stays NaN (a diverged value stays visible), -0 stays -0
         *p = v;
     }
 }
 
-// dy *= (y > 0), in place: the gradient of out = relu(u) with respect to u, where y is the stored output
+// dy = (y <= 0) ? 0 : dy, in place: the gradient of out = relu(u) with respect to u, where y is the stored output.  ATen's
+// threshold_backward: a NaN y passes the gradient.
 __global__ __launch_bounds__(256) void relu_bwd_kernel(bf16* dy, long ld_dy, const bf16* y, long ld_y, long M, int C) {
     const int cgs = C >> 3;
     const long total = M * cgs;
@@ -67,7 +68,7 @@ __global__ __launch_bounds__(256) void relu_bwd_kernel(bf16* dy, long ld_dy, con
         const bf16x8 yy = *reinterpret_cast<const bf16x8*>(y + m * ld_y + cg * 8);
         bf16x8 v = *p;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = (float)yy[j] > 0.f ? v[j] : (bf16)0.f;
+        for (int j = 0; j < 8; ++j) v[j] = (float)yy[j] <= 0.f ? (bf16)0.f : v[j];
         *p = v;
     }
 }
@@ -351,7 +352,7 @@ extern "C" int ep24_incr_i64(int64_t* p, void* stream) {
 }
 
 extern "C" int ep24_colstats(const void* x, int64_t ld, int64_t* stats, int64_t ld_stats, int64_t M, int C, void* stream) {
-    EP24_REQUIRE(x && stats && C % 8 == 0 && C <= 2048 && ld % 8 == 0 && M > 0 && ld_stats >= C, EP24_E_ARG, "colstats: bad arguments");
+    EP24_REQUIRE(x && stats && C > 0 && C % 8 == 0 && C <= 2048 && ld % 8 == 0 && M > 0 && ld_stats >= C, EP24_E_ARG, "colstats: bad arguments");
     long blocks = (M + 15) / 16;
     if (blocks > 1024) blocks = 1024;
     hipLaunchKernelGGL(colstats_kernel, dim3((unsigned)blocks), dim3(256), 0, S_, (const bf16*)x, (long)ld, (long long*)stats, (long)ld_stats,

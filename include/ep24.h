@@ -228,7 +228,9 @@ int ep24_conv1x1_dgrad_bnr_bf16(const void* dy, int64_t ld_dy, const void* wt, v
  * followed by a 1x1 BaseConv; `depthwise=True` of CSPDarknet / Bottleneck / YOLOPAFPN / YOLOXHead, darknet.py:107, network_blocks.py:92,
  * yolo_pafpn.py:30, yolo_head_24p.py:45 - in no BASELINE configuration).  HBM-bound elementwise kernels (csrc/dwconv.hip): NHWC bf16
  * activations, w = the fp32 master [C][3][3] read in place, fp32 accumulation, stride 1 or 2, pad 1; C % 8 == 0.
- *   fwd:   z = conv(x, w); `stats` as ep24_conv_fwd_bf16 ([replicas][2][C] fixed-point batch statistics of z), or NULL.
+ *   fwd:   z = conv(x, w); `stats` as ep24_conv_fwd_bf16 ([replicas][2][C] fixed-point batch statistics, ADDED to what the buffer
+ *          holds, workgroup b into replica b % replicas), or NULL.  As in ep24_conv_fwd_bf16 the statistics are those of the fp32
+ *          accumulator BEFORE its rounding to bf16, not of the stored z (tests/test_gpu_backbone_exact.py pins this).
  *   dgrad: dx (+)= the input gradient from dz [B,OH,OW,C].
  *   wgrad: slab [splits][C][9] fp32 = per-workgroup partial sums of dw, splits = ep24_dwconv_wgrad_splits(...) (fixed by the shape);
  *          ep24_wgrad_reduce folds them in order into the flat gradient, as for every other weight gradient (no atomics).
@@ -1073,7 +1075,9 @@ int ep24_paste_u8(const float* pre_images, const float* out_labels, const int32_
 int ep24_im2col_bf16(const float* images, void* rows, int64_t ld, int B, int C, int H, int W, int k, int stride, int pad,
                      void* stream);
 /* Bottleneck tail "out += identity; out = relu(out)" (darknet.py:266-268): the sum comes out of ep24_bn_act_fwd (act 0 +
- * residual); relu_fwd clamps it in place, relu_bwd masks the incoming gradient in place with the stored output (y > 0). */
+ * residual); relu_fwd clamps it in place (x < 0 -> +0; NaN stays NaN and -0 stays -0, as ATen's relu: a diverged value stays
+ * visible), relu_bwd masks the incoming gradient in place with the stored output (y <= 0 -> +0, as ATen's threshold_backward: a NaN y
+ * passes the gradient). */
 int ep24_relu_fwd(void* y, int64_t ld, int64_t M, int C, void* stream);
 int ep24_relu_bwd(void* dy, int64_t ld_dy, const void* y, int64_t ld_y, int64_t M, int C, void* stream);
 /* nn.MaxPool2d(kernel_size=3, stride=2, padding=1) (darknet.py:303) on NHWC bf16; idx [B*OH*OW*C] uint8 = winning tap
