@@ -17,12 +17,7 @@ namespace {
 
 // kernel_opts of the _ex entry points (include/ep24.h): per call, no process-wide state
 constexpr int KOPT_TILED = 1, KOPT_NARROW_EPI = 2, KOPT_PER_CLASS = 4;     // bit 2: a stride-2 input gradient as one launch per parity class
-constexpr int KOPT_GRING = 16;             // bit 4: layers of the tiled kernel that fill the chip with 256 x 128 tiles run in the ring without a
-                                           // patch instead (conv_ring.hip; measured SLOWER on every layer of YOLOX-l at B = 20,
-                                           // profiles/r04_ring_generic_ab.txt: an A/B option, off by default)
-constexpr int KOPT_RING32 = 32;            // bit 5: the ring's consumers multiply with v_mfma_f32_32x32x16_bf16 instead of 16x16x32 (an A/B option: 12 % fewer
-                                           // cycles per step, a 9 % lower clock under load - slower in the step, profiles/r04_ring_ab.txt)
-constexpr int KOPT_NARROW = 64;            // bit 6: A/B option - 3x3 stride-1 layers in the ring with the NARROW tile (256 x 64; also the 20 x 20 level and N = 64)
+constexpr int KOPT_REMOVED = 16 | 32 | 64; // bits 4 - 6: reserved, refused (the ring without a patch, its 32 x 32 x 16 consumers, its 256 x 64 tile: DESIGN.md section 4)
 constexpr int KOPT_NO_DEEP = 128;          // bit 7: A/B option - no three-stage form of the tiled kernel (the 20 x 20 level runs in 64-wide two-stage tiles, as before round 4)
 constexpr int KOPT_TILED256 = 256;         // bit 8: A/B option - 1x1 stride-1 layers with 128 < K <= 256 and M < 100 000 in the tiled kernel, as before the streaming
                                            // kernel's weight tile was requested in one batch (round 5: since then it wins there too, profiles/r05_xf_ab.txt)
@@ -835,7 +830,7 @@ int check_extents(const IgemmArgs& a) {
     return EP24_OK;
 }
 
-// dry = true: no launch, *kernel_id receives the kernel the shape dispatches to (0 tiled, 1 halo patch, 2 streaming, 3 loader / consumer ring, 4 ring without a patch, 5 narrow ring, 6 weights in registers)
+// dry = true: no launch, *kernel_id receives the kernel the shape dispatches to (0 tiled, 1 halo patch, 2 streaming, 3 loader / consumer ring, 6 weights in registers; 4 and 5 are reserved and never returned)
 void prepare(IgemmArgs& a, int kernel_opts) {
     a.narrow_epi = (kernel_opts & KOPT_NARROW_EPI) ? 1 : 0;
     a.src_bytes = (unsigned)((((long)a.B * a.SH * a.SW - 1) * a.ld_src + a.K) * 2);
@@ -888,11 +883,8 @@ int launch_multi(IgemmArgs* cls, int n, hipStream_t stream, int kernel_opts) {
 }
 
 int launch(IgemmArgs a, bool out_f32, hipStream_t stream, int kernel_opts = 0, bool dry = false, int* kernel_id = nullptr) {
-#ifndef EP24_AB_VARIANTS
-    EP24_REQUIRE(!(kernel_opts & (KOPT_GRING | KOPT_RING32 | KOPT_NARROW)), EP24_E_UNSUPPORTED,
-                 "conv: kernel_opts bits 4 - 6 select variants that were measured, lost and left the product library (round 5); "
-                 "build the A/B library with `make -C exploration-of-potential_amd/csrc variants` and load it through EP24_LIB");
-#endif
+    EP24_REQUIRE(!(kernel_opts & KOPT_REMOVED), EP24_E_UNSUPPORTED,
+                 "conv: kernel_opts bits 4 - 6 selected variants that were measured, lost and removed; their source is at commit 6cc7180");
     if (!dry) { if (int rc = check_extents(a)) return rc; }
     prepare(a, kernel_opts);
     const bool plain_dst = a.dsy == 1 && a.dsx == 1 && a.dy0 == 0 && a.dx0 == 0 && a.DW == a.GW && a.dp0 == 0 && a.dbs == (long)a.GH * a.GW;
@@ -935,19 +927,14 @@ int launch(IgemmArgs a, bool out_f32, hipStream_t stream, int kernel_opts = 0, b
     if (a.T == 9 && a.sy == 1 && a.sx == 1 && a.GH == a.SH && a.GW == a.SW && plain_dst && !out_f32 && ((!a.bias && !a.epi_infer) || infer_ring) &&
         !(kernel_opts & KOPT_TILED)) {
         int prc = EP24_OK;
-        int ring = 0;
         if (!a.epi_infer && !(kernel_opts & KOPT_NO_WREG) && launch_wreg(a, stream, dry, &prc)) {      // N, K <= 64: the weights live in registers
             if (dry) { *kernel_id = 6; return EP24_OK; }
             if (prc) return prc;
             EP24_LAUNCH_CHECK("ep24_conv_wreg");
             return EP24_OK;
         }
-        if (!(kernel_opts & KOPT_PATCH8)) {
-            if (kernel_opts & KOPT_NARROW) ring = launch_ring(a, stream, dry, &prc, true, true);
-            if (!ring) ring = launch_ring(a, stream, dry, &prc, (kernel_opts & KOPT_RING32) == 0, false);
-        }
-        if (ring) {
-            if (dry) { *kernel_id = ring == 2 ? 5 : 3; return EP24_OK; }
+        if (!(kernel_opts & KOPT_PATCH8) && launch_ring(a, stream, dry, &prc)) {
+            if (dry) { *kernel_id = 3; return EP24_OK; }
             if (prc) return prc;
             EP24_LAUNCH_CHECK("ep24_conv_ring");
             return EP24_OK;
@@ -956,16 +943,6 @@ int launch(IgemmArgs a, bool out_f32, hipStream_t stream, int kernel_opts = 0, b
             if (dry) { *kernel_id = 1; return EP24_OK; }
             if (prc) return prc;
             EP24_LAUNCH_CHECK("ep24_conv_patch");
-            return EP24_OK;
-        }
-    }
-    // A/B option: everything else that fills the chip with 256 x 128 tiles and stores bf16 in the ring without a patch
-    if (!out_f32 && (kernel_opts & KOPT_GRING) && !(kernel_opts & KOPT_TILED) && a.T * ep24_cdiv(a.K, BK) >= 4) {
-        int grc = EP24_OK;
-        if (launch_ring_generic(a, stream, dry, &grc)) {
-            if (dry) { *kernel_id = 4; return EP24_OK; }
-            if (grc) return grc;
-            EP24_LAUNCH_CHECK("ep24_conv_ring_generic");
             return EP24_OK;
         }
     }

@@ -713,18 +713,15 @@ class Engine:
         return Act(Buf(self.dev, self.B * H * W, ld or C, self.dtype), 0, C, self.B, H, W)
 
     def _kopt(self, name, args):
-        """conv_fwd_bf16 / conv_dgrad_bf16 with the plan's kernel options (PlanOptions.conv_kernel_opts != 0: the _ex entry points);
-        bit 8 of the options is the weight gradient's bit 0 (its loader / consumer ring form, an A/B option)."""
+        """conv_fwd_bf16 / conv_dgrad_bf16 with the plan's kernel options (PlanOptions.conv_kernel_opts != 0: the _ex entry points)."""
         ko = self.options.conv_kernel_opts
-        if ko & 0xFF and name in ("conv_fwd_bf16", "conv_dgrad_bf16"):
-            return name + "_ex", tuple(args) + (ko & 0xFF,)
-        if ko & 0x100 and name in ("conv_wgrad_slab_bf16", "side:conv_wgrad_slab_bf16"):
-            return name + "_ex", tuple(args) + (1,)
+        if ko and name in ("conv_fwd_bf16", "conv_dgrad_bf16"):
+            return name + "_ex", tuple(args) + (ko,)
         return name, tuple(args)
 
     def _wsplits(self, B, H, W, cin, cout, k, s):
-        """Pixel splits of a weight-gradient launch (the slab it needs), for the kernel the plan's options select."""
-        return _lib.lib().fn["ep24_conv_wgrad_splits_ex"](B, H, W, cin, cout, k, s, 1 if self.options.conv_kernel_opts & 0x100 else 0)
+        """Pixel splits of a weight-gradient launch (the slab it needs)."""
+        return _lib.lib().fn["ep24_conv_wgrad_splits"](B, H, W, cin, cout, k, s)
 
     def _f(self, name, *args, ev=None):
         """Append a forward launch; `ev` = the (name, args) that replaces it in the eval-mode list (default: the same)."""
@@ -1230,7 +1227,7 @@ class Engine:
         tail of backward, plans without grouping)."""
         x, seg, cout = u.x, u.seg, u.C
         B, H, W = x.B, x.H, x.W
-        if self.options.group_wgrad and not u.focus and not self._wg_tail and not (self.options.conv_kernel_opts & 0x100):
+        if self.options.group_wgrad and not u.focus and not self._wg_tail:
             # csrc/conv_wgrad.hip wgrad_group_kernel; its slab is allotted when the group is launched (the split count is the group's)
             self._pend_wgrad(dict(x=x.ptr, ld_x=x.ld, dz=u.dz, ld_dy=cout, ld_dw=seg.taps * seg.cin, cout_valid=cout, cin_valid=seg.cin,
                                   B=B, H=H, W=W, cin=u.cin, cout=cout, k=u.k, s=u.s, seg=seg, idx=u.idx))

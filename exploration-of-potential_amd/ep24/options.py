@@ -23,7 +23,10 @@ class PlanOptions:
     parallel_head: bool = True         # backward of head levels 1, 2 on the weight-gradient lane
     capture_side: bool = False         # cross-stream edges inside captured graphs (experimental; faulted on ROCm 7.2)
     fold_bn_eval: bool = True          # eval mode: BatchNorm folded into the conv (one launch per unit)
-    conv_kernel_opts: int = 0          # bit 0: 3x3 stride-1 layers through the generic tiled kernel, bit 1: 8-byte epilogue stores
+    conv_kernel_opts: int = 0          # kernel_opts of the conv _ex entry points (include/ep24.h), forward and input gradient.  bit 0: 3x3 stride-1 layers
+                                       # through the generic tiled kernel, bit 1: 8-byte epilogue stores, bit 2: a stride-2 input gradient as one launch per
+                                       # parity class, bit 3: 3x3 stride-1 layers through the 8-wave halo-patch kernel, bit 7: the tiled kernel without its
+                                       # three-stage form.  Any other bit is a ValueError
     wgrad_group_steps: int = 100       # 64-pixel steps a workgroup of a grouped weight-gradient launch keeps at least (swept again at the end of round 5,
                                        # when the lane had become co-critical: 60 / 75 / 90 / 100 / 120 / 160 / 250 -> 19.94 / 19.55 / 19.41 / 19.44 / 19.44 / 19.58 / 19.77 ms
                                        # for the headline network; 90 costs the VGG backbone 7 % (484 against 521 - 523 images/s at 100 / 120): 100)
@@ -48,6 +51,11 @@ class PlanOptions:
     chunked_update: bool = True        # the optimizer update in pieces on the weight-gradient lane, each as soon as its gradients are complete
 
     LAYOUT_FIELDS: ClassVar[tuple] = ("merge_csp", "merge_csp_shortcut", "merge_head")     # these decide the flat parameter layout
+    CONV_KERNEL_OPTS: ClassVar[int] = 0x8F     # bits 0, 1, 2, 3 and 7: what the engine forwards and the library runs
+
+    def __post_init__(self):
+        if self.conv_kernel_opts & ~self.CONV_KERNEL_OPTS:
+            raise ValueError("conv_kernel_opts=%d: only bits 0, 1, 2, 3 and 7 select a kernel (mask 0x%X)" % (self.conv_kernel_opts, self.CONV_KERNEL_OPTS))
 
     def with_(self, **kw):
         return replace(self, **kw)

@@ -62,14 +62,11 @@ int ep24_conv_fwd_bf16(const void* x, int64_t ld_x, const void* w, void* y, int6
  * or a destination that is not 16-byte aligned, in the tiled, ring and 8-wave kernels alike);
  * bit 2: a stride-2 input gradient runs as one launch per parity class (four) instead of one merged launch; bit 3: the 3x3
  * stride-1 layers run in the 8-wave lockstep halo-patch kernel (csrc/conv_patch.hip) instead of the loader / consumer ring
- * (csrc/conv_ring.hip, the default since round 4); bit 4: layers of the tiled kernel that fill the chip with 256 x 128 tiles run in
- * the ring without a patch (measured slower on every layer of YOLOX-l at B = 20: off by default); bit 5: the ring's consumers
- * multiply with v_mfma_f32_32x32x16_bf16 instead of v_mfma_f32_16x16x32_bf16 (same products; the fp32 sum of a 64-channel chunk in
- * four steps of 16 instead of two of 32, so results differ from the other kernels in the last bit; fewer cycles, lower clock: an
- * A/B option); bit 6: the ring with its NARROW tile (256 pixels x 64 channels, four consumers of 64 x 64, a weight-ring stage per
- * tap and loaders five steps ahead) for every 3x3 stride-1 layer with at least 128 such tiles - also the 20 x 20 level and N = 64,
- * which the 256 x 128 ring does not take (bit-identical results; measured slower than the tiled kernel it would replace: an A/B
- * option); bit 7: the tiled kernel without its three-stage form (round 4: layers whose 128-wide tiles leave at most one workgroup per
+ * (csrc/conv_ring.hip, the default since round 4);
+ * bit 4: reserved, refused (EP24_E_UNSUPPORTED; it selected the ring without a patch);
+ * bit 5: reserved, refused (the ring's 32 x 32 x 16 consumers);
+ * bit 6: reserved, refused (the ring's 256 x 64 tile);
+ * bit 7: the tiled kernel without its three-stage form (round 4: layers whose 128-wide tiles leave at most one workgroup per
  * CU - the 20 x 20 level at B = 20 - run in 128-wide tiles with three LDS stages and two tiles in flight; with bit 7 they run in 64-wide
  * two-stage tiles as before; bit-identical results); bit 8: 1x1 stride-1 layers with 128 < K <= 256 and fewer than 100 000 pixels run
  * in the tiled kernel, as they did before the streaming kernel's weight tile was requested in one batch (round 5: the streaming kernel
@@ -79,9 +76,9 @@ int ep24_conv_fwd_bf16(const void* x, int64_t ld_x, const void* w, void* y, int6
  * persistent workgroups, one LDS window per tap row; bit-identical outputs, the batch statistics equal to fp32 summation order; the
  * default for such layers with at least 65 536 pixels, an image at least 32 wide and a plain first-writer destination).  kernel_opts = 0 is exactly ep24_conv_fwd_bf16 / ep24_conv_dgrad_bf16, and every default kernel of a 3x3 stride-1
  * layer (ring, 8-wave halo patch, tiled) gives bit-identical results. */
-/* Round 5: bits 4, 5 and 6 (and bit 0 of the weight gradient's kernel_opts) select variants that were built, measured and lost in
- * rounds 3 - 4; they left the product library, which answers EP24_E_UNSUPPORTED for them.  `make -C csrc variants` builds
- * libep24_variants.so with them (EP24_LIB selects it); ep24_ab_variants() says which kind of library is loaded. */
+/* Bits 4, 5 and 6 (and bit 0 of the weight gradient's kernel_opts) selected variants that were built, measured and lost in rounds
+ * 3 - 4; they were removed, their source is at commit 6cc7180. */
+/* Always 0: kept so that version-3 callers keep binding. */
 int ep24_ab_variants(void);
 int ep24_conv_fwd_bf16_ex(const void* x, int64_t ld_x, const void* w, void* y, int64_t ld_y, int y_f32,
                           int64_t y_batch_rows, int64_t y_row0, const float* bias, int64_t* stats, int stats_replicas,
@@ -91,7 +88,7 @@ int ep24_conv_dgrad_bf16_ex(const void* dy, int64_t ld_dy, const void* wt, void*
 
 /* The 3x3 stride-1 layers run as a loader / consumer ring (csrc/conv_ring.hip: 4 MFMA waves fed by 4 LDS-DMA waves through counters
  * in LDS).  Every wait on a counter is a bounded spin; this returns how many of them have given up since the library was loaded
- * (reads a device word: synchronises with the device; the weight-gradient ring of csrc/conv_wgrad.hip counts in).  Always 0 unless
+ * (reads a device word: synchronises with the device; the grid-wide wait of the fused BatchNorm backward counts in).  Always 0 unless
  * the hand-off protocol is broken - tests assert it. */
 int ep24_conv_ring_timeouts(void);
 
@@ -108,9 +105,10 @@ int ep24_conv_dgrad_bnr_bf16(const void* dy, int64_t ld_dy, const void* wt, void
 /* Which device kernel ep24_conv_fwd_bf16 (dgrad = 0) / ep24_conv_dgrad_bf16 (dgrad = 1, stride 1) launches for a shape - the
  * library's own dispatch rule, for reports (bench.py attributes launch times to kernels with it).  Returns 0 =
  * igemm_dma_kernel (generic tiled), 1 = conv_patch_kernel (halo patch, 8 waves in lockstep), 2 = igemm_stream_kernel (1x1
- * streaming), 3 = conv_ring_kernel (halo patch as a loader / consumer ring), 4 = conv_ring_generic_kernel (the ring without a
- * patch; only with kernel_opts bit 4), 5 = conv_ring_kernel with the narrow tile (only with kernel_opts bit 6), 6 = conv_wreg_kernel
+ * streaming), 3 = conv_ring_kernel (halo patch as a loader / consumer ring), 6 = conv_wreg_kernel
  * (3x3 stride-1, at most 64 channels on either side: weights in registers), < 0 on error.
+ * 4: reserved, never returned.
+ * 5: reserved, never returned.
  * y_f32 / has_bias as in ep24_conv_fwd_bf16 (both 0 for dgrad). */
 int ep24_conv_kernel_for(int dgrad, int B, int H, int W, int Cin, int Cout, int ksize, int stride, int y_f32, int has_bias);
 /* ... and for the _ex entry points with the given kernel_opts. */
@@ -147,9 +145,7 @@ int ep24_conv_wgrad_splits(int B, int H, int W, int Cin, int Cout, int ksize, in
 int ep24_conv_wgrad_slab_bf16(const void* x, int64_t ld_x, const void* dy, int64_t ld_dy, float* slab, int64_t slab_floats,
                               int64_t ld_dw, int cout_valid, int cin_valid,
                               int B, int H, int W, int Cin, int Cout, int ksize, int stride, void* stream);
-/* The same two with an explicit kernel choice per call (A/B timing, tests): kernel_opts bit 0 = the loader / consumer ring form
- * (layers with Cout >= 256 whose (tile, split) grid fills the chip; csrc/conv_wgrad.hip, round 4: measured 10 % slower than
- * wgrad_kernel, off by default).  The split count - and with it the slab size - depends on the kernel: ask with the same options. */
+/* The same two with a kernel_opts argument.  Bit 0: reserved, refused (EP24_E_UNSUPPORTED at the launch; it selected the weight gradient as a ring). */
 int ep24_conv_wgrad_splits_ex(int B, int H, int W, int Cin, int Cout, int ksize, int stride, int kernel_opts);
 int ep24_conv_wgrad_slab_bf16_ex(const void* x, int64_t ld_x, const void* dy, int64_t ld_dy, float* slab, int64_t slab_floats,
                                  int64_t ld_dw, int cout_valid, int cin_valid, int B, int H, int W, int Cin, int Cout, int ksize,

@@ -41,6 +41,30 @@ def test_no_undeclared_ep24_exports():
     assert exported == declared, exported ^ declared
 
 
+def test_removed_conv_variants_are_refused():
+    """kernel_opts bits 4 - 6 of the conv _ex entry points selected kernel variants that were removed: the dry-run dispatch query refuses
+    them loudly, the bits that remain dispatch as before, and ep24_ab_variants() stays 0.  The calls run on a thread of their own: the
+    library's last-error text is per thread, and other tests expect this thread's to stay empty."""
+    import threading
+    L = _lib.lib()
+    kernel_for = L.fn["ep24_conv_kernel_for_ex"]
+    refused, ids = {}, {}
+
+    def calls():
+        for k in (3, 1):                                                   # the 20 x 40 x 40 x 256 -> 256 stride-1 layers
+            for opts in (16, 32, 64, 16 | 1):
+                refused[k, opts] = (kernel_for(0, 20, 40, 40, 256, 256, k, 1, 0, 0, opts), L.last_error())
+            ids[k] = [kernel_for(0, 20, 40, 40, 256, 256, k, 1, 0, 0, opts) for opts in (0, 8, 1, 512)]
+    th = threading.Thread(target=calls)
+    th.start()
+    th.join()
+    assert len(refused) == 8
+    for key, (rc, text) in refused.items():
+        assert rc < 0 and text and "removed" in text, (key, rc, text)
+    assert ids == {3: [3, 1, 0, 3], 1: [2, 2, 2, 2]}
+    assert L.fn["ep24_ab_variants"]() == 0
+
+
 def test_product_path_refuses_to_run_without_gpu():
     import torch
     if torch.cuda.is_available():

@@ -126,14 +126,6 @@ HOT_SHAPES = [  # B, H, Cin, Cout, k, s[, W]
     # offset): rows past M in the last block and a whole block past the end (odd unit count), an N tail, K = 64 (two K steps),
     # a K tail inside a step (K = 120), two K halves with a tail (K = 200, M large enough for the streaming form)
     (3, 50, 64, 72, 1, 1, 50), (5, 36, 120, 200, 1, 1, 36), (17, 80, 200, 136, 1, 1, 79),
-    # the ring without a patch (round 4; kernel_opts bit 4; an 8th value is the kernel id the shape must dispatch to with it): the 4-step 1x1 layer of the
-    # 40x40 level, a 1x1 layer with M, N and K tails, a stride-2 3x3 layer with a K tail
-    (20, 40, 256, 256, 1, 1, 40, 4), (13, 50, 200, 264, 1, 1, 47, 4), (20, 90, 72, 136, 3, 2, 86, 4),
-    # the NARROW ring (256 x 64 tiles, kernel_opts bit 6, an A/B option; a 9th value = the kernel_opts the id is asked under): the 20 x 20
-    # level of YOLOX-l, which 256 x 128 tiles do not spread over the chip; M and N tails; a K tail over two patch buffers; N = 64 with one chunk and the widest patch
-    # (W = 160: three patch pieces per loader and step); N = 64 with an M tail
-    (20, 20, 512, 512, 3, 1, 20, 5, 64), (21, 20, 256, 200, 3, 1, 19, 5, 64), (21, 20, 72, 256, 3, 1, 19, 5, 64), (4, 160, 64, 64, 3, 1, 160, 5, 64),
-    (7, 52, 64, 64, 3, 1, 100, 5, 64), (20, 40, 256, 256, 3, 1, 40, 5, 64),
 ]
 
 
@@ -165,19 +157,7 @@ def test_conv_hot_shapes(shape):
     gy = rnd(B, Cout, OH, OW, seed=3)
     y_ref, dx_ref, dw_ref = _torch_conv_ref(x, w, gy, s, pad)
     M = B * OH * OW
-    # Round 5: the variants that lost twice (ring without a patch = bit 4, 32x32x16 consumers = bit 5, narrow ring = bit 6, the weight
-    # gradient as a ring) left the product library; `make variants` + EP24_LIB=.../libep24_variants.so brings them back for this test
-    have_variants = fn["ep24_ab_variants"]() == 1
-    if len(shape) > 7 and not have_variants:
-        # the product library refuses the bits loudly (also in the dry-run query)
-        assert fn["ep24_conv_kernel_for_ex"](0, B, H, W, Cin, Cout, k, s, 0, 0, shape[8] if len(shape) > 8 else 16) < 0
-        assert "make" in _lib.lib().last_error() and "variants" in _lib.lib().last_error()
-        pytest.skip("variant shape: needs the A/B library (make variants)")
-    if len(shape) > 7:
-        assert fn["ep24_conv_kernel_for_ex"](0, B, H, W, Cin, Cout, k, s, 0, 0, shape[8] if len(shape) > 8 else 16) == shape[7]
-        if shape[7] == 5:                                                  # ... which no layer takes by default
-            assert fn["ep24_conv_kernel_for_ex"](0, B, H, W, Cin, Cout, k, s, 0, 0, 0) in (0, 1, 3)
-    elif len(shape) > 6:
+    if len(shape) > 6:
         want = (6 if max(Cin, Cout) <= 64 else 3) if k == 3 else 2       # 3: the loader / consumer ring (round 4), 6: weights in registers (round 5), 2: streaming
         assert M % 256 != 0 and fn["ep24_conv_kernel_for"](0, B, H, W, Cin, Cout, k, s, 0, 0) == want, "meant to exercise the ring / streaming kernel's tails"
 
@@ -189,13 +169,9 @@ def test_conv_hot_shapes(shape):
     outs = {}
     # kernel_opts of the _ex entry points (per call, no global switch): 0 = the shape's default (3x3 stride-1: the loader / consumer
     # ring of conv_ring.hip where it fits), bit 3 = the 8-wave halo-patch kernel instead, bit 0 = the generic tiled kernel
-    # other layers: bit 4 sends those that fill the chip with 256 x 128 tiles to the ring without a patch (kernel id 4; an A/B option)
-    # 3x3 stride-1: the default is the ring with 16x16x32 consumers; bit 5 = its 32x32x16 form (key 3), bit 3 = the 8-wave kernel
-    # key 4: the narrow ring where it fits; key 5 (bits 0 + 7): the tiled kernel WITHOUT its three-stage form (the 20 x 20 level)
+    # key 5 (bits 0 + 7): the tiled kernel WITHOUT its three-stage form (the 20 x 20 level)
     # key 6 (bit 9): a 3x3 stride-1 layer with <= 64 channels in the kernel it ran in before the weights-in-registers kernel
-    variants = ((0, 1), (2, 0), (3, 32), (1, 8), (4, 64), (5, 129), (6, 512)) if (k == 3 and s == 1) else ((0, 128), (2, 0), (5, 16))
-    if not have_variants:
-        variants = tuple(v for v in variants if not (v[1] & (16 | 32 | 64)))
+    variants = ((0, 1), (2, 0), (1, 8), (5, 129), (6, 512)) if (k == 3 and s == 1) else ((0, 128), (2, 0))
     for patch, ko in variants:
         y = torch.zeros(B, OH, OW, Cout, dtype=BF, device=DEV)
         stats = torch.zeros(R, 2, Cout, dtype=torch.int64, device=DEV)
@@ -218,18 +194,8 @@ def test_conv_hot_shapes(shape):
     # gradients (plain and accumulated), whichever kernel ran; the batch statistics are sums of per-tile fp32 partial sums, and the
     # tiles differ (256 rows against 128): equal to fp32 summation order
     for other in outs:
-        if other == 3 and have_variants and fn["ep24_conv_kernel_for_ex"](0, B, H, W, Cin, Cout, k, s, 0, 0, 32) == 3:
-            # The 32x32x16 consumers add the SAME products, the fp32 sum of a 64-channel chunk in four k-steps of 16 instead of two of
-            # 32: fp32 sums agree to rounding, so after the one rounding to bf16 an element differs by at most one bf16 ulp (2^-8
-            # relative; an element that is itself a cancelled sum by 1e-5 of the tensor's range), and only a few per cent do at all.
-            for a_, b_ in zip(outs[0][:3], outs[3][:3]):
-                a32, b32 = a_.float(), b_.float()
-                d = (a32 - b32).abs()
-                assert bool((d <= 2.0 ** -8 * b32.abs() + 1e-5 * float(b32.abs().max())).all()), float(d.max())
-                assert float((d > 0).float().mean()) < 0.05, float((d > 0).float().mean())
-        else:
-            for a_, b_ in zip(outs[0][:3], outs[other][:3]):
-                assert torch.equal(a_, b_), other
+        for a_, b_ in zip(outs[0][:3], outs[other][:3]):
+            assert torch.equal(a_, b_), other
         sa, sb = outs[0][3].sum(0).double(), outs[other][3].sum(0).double()
         assert float((sa - sb).abs().max()) <= 1e-5 * float(sb.abs().max()), other
     if k == 3 and s == 1 and max(Cin, Cout) <= 64 and M >= 65536:
@@ -241,34 +207,29 @@ def test_conv_hot_shapes(shape):
         st_again = torch.zeros(R, 2, Cout, dtype=torch.int64, device=DEV)
         call("conv_fwd_bf16_ex", ptr(xd), Cin, ptr(wf), ptr(y_again), Cout, 0, 0, 0, None, ptr(st_again), R, B, H, W, Cin, Cout, k, s, 0, sp())
         assert torch.equal(y_again, outs[2][0]) and torch.equal(st_again, outs[2][3])
-    if 3 in outs:                                                          # ... and is bitwise reproducible run to run
-        y_again = torch.zeros(B, OH, OW, Cout, dtype=BF, device=DEV)
-        call("conv_fwd_bf16_ex", ptr(xd), Cin, ptr(wf), ptr(y_again), Cout, 0, 0, 0, None, None, R, B, H, W, Cin, Cout, k, s, 32, sp())
-        assert torch.equal(y_again, outs[3][0])
     # no bounded wait of the ring kernel ever gave up (a protocol error would show here even if the numbers happened to agree)
     assert fn["ep24_conv_ring_timeouts"]() == 0
 
-    # weight gradient: wgrad_kernel (the default) and, where the layer is eligible (Cout >= 256, the grid fills the chip), its loader /
-    # consumer ring form (kernel_opts bit 0, an A/B option).  The kernels may split the pixels differently: equal to fp32 summation
-    # order; each is bitwise reproducible.
+    # weight gradient: wgrad_kernel, bitwise reproducible
     numel = Cout * k * k * Cin
-    grads = {}
-    for wo in ((0, 1) if have_variants else (0,)):
-        splits = fn["ep24_conv_wgrad_splits_ex"](B, H, W, Cin, Cout, k, s, wo)
-        reps = []
-        for rep in range(2):
-            slab = torch.full((splits * numel,), float("nan"), device=DEV)
-            g = torch.zeros(numel, device=DEV)
-            desc = torch.tensor([[0, numel, splits, 0]], dtype=torch.int64, device=DEV)
-            call("conv_wgrad_slab_bf16_ex", ptr(xd), Cin, ptr(gyd), Cout, ptr(slab), splits * numel, k * k * Cin, Cout, Cin, B, H, W, Cin, Cout, k, s, wo, sp())
-            call("wgrad_reduce", ptr(desc), 1, numel, ptr(g), ptr(slab), sp())
-            reps.append(g)
-        close(reps[0].view(Cout, k, k, Cin).permute(0, 3, 1, 2), dw_ref, rel=5e-3)
-        if len(reps) == 2:
-            assert torch.equal(reps[0], reps[1])
-        grads[wo] = (reps[0], splits)
-    if have_variants:
-        assert float((grads[0][0] - grads[1][0]).abs().max()) <= 2e-5 * float(grads[1][0].abs().max()), (grads[0][1], grads[1][1])
+    splits = fn["ep24_conv_wgrad_splits_ex"](B, H, W, Cin, Cout, k, s, 0)
+    reps = []
+    for rep in range(2):
+        slab = torch.full((splits * numel,), float("nan"), device=DEV)
+        g = torch.zeros(numel, device=DEV)
+        desc = torch.tensor([[0, numel, splits, 0]], dtype=torch.int64, device=DEV)
+        call("conv_wgrad_slab_bf16_ex", ptr(xd), Cin, ptr(gyd), Cout, ptr(slab), splits * numel, k * k * Cin, Cout, Cin, B, H, W, Cin, Cout, k, s, 0, sp())
+        call("wgrad_reduce", ptr(desc), 1, numel, ptr(g), ptr(slab), sp())
+        reps.append(g)
+    close(reps[0].view(Cout, k, k, Cin).permute(0, 3, 1, 2), dw_ref, rel=5e-3)
+    assert torch.equal(reps[0], reps[1])
+    if shape == (3, 50, 64, 72, 1, 1, 50):
+        # kernel_opts bit 0 of the weight gradient (its removed ring form) is refused before anything is launched: the slab is untouched
+        slab = torch.full((splits * numel,), float("nan"), device=DEV)
+        assert fn["ep24_conv_wgrad_slab_bf16_ex"](ptr(xd), Cin, ptr(gyd), Cout, ptr(slab), splits * numel, k * k * Cin, Cout, Cin, B, H, W, Cin, Cout, k, s, 1, sp()) < 0
+        assert "removed" in _lib.lib().last_error()
+        torch.cuda.synchronize()
+        assert bool(torch.isnan(slab).all())
     assert fn["ep24_conv_ring_timeouts"]() == 0
 
 

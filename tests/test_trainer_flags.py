@@ -112,6 +112,13 @@ def test_plan_options_are_per_model_objects():
         raise AssertionError("unknown option accepted")
     except ValueError:
         pass
+    for text in ("conv_kernel_opts=256", "conv_kernel_opts=16"):        # a kernel option the library would refuse at its first launch
+        try:
+            PlanOptions.parse(text)
+            raise AssertionError(text + " accepted")
+        except ValueError:
+            pass
+    assert PlanOptions.parse("conv_kernel_opts=1").conv_kernel_opts == 1 and PlanOptions.parse("conv_kernel_opts=137").conv_kernel_opts == 137
     a, b = torch.nn.Linear(2, 2), torch.nn.Linear(2, 2)
     set_options(a, o)
     assert get_options(a) is o and get_options(b) is DEFAULT          # another model in the same process is untouched

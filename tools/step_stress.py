@@ -21,7 +21,7 @@ ap.add_argument("--batch", type=int, default=20)
 ap.add_argument("--size", type=int, default=640)
 ap.add_argument("--eager", action="store_true")
 ap.add_argument("--backbone", default="darknet", choices=["darknet", "resnet", "densenet", "vgg"])
-ap.add_argument("--kernel-opts", type=int, default=0, help="PlanOptions.conv_kernel_opts: bit0 tiled kernel instead of the halo-patch kernel, bit1 narrow epilogue")
+ap.add_argument("--kernel-opts", type=int, default=0, help="PlanOptions.conv_kernel_opts (bits 0, 1, 2, 3 and 7): bit0 tiled kernel instead of the halo-patch kernels, bit1 narrow epilogue")
 a = ap.parse_args()
 DEV = torch.device("cuda", 0)
 
