@@ -31,7 +31,9 @@ __global__ __launch_bounds__(256) void bn_act_infer_kernel(const bf16* z, long l
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const float u = fmaf((float)v[j], sc[g * 8 + j], sh[g * 8 + j]);
-            o[j] = (bf16)(act_fwd(u, act) + (res ? (float)r[j] : 0.f));
+            // ReLU as ATen writes it: NaN stays NaN (fmaxf would hide a diverged value behind a 0), -0 stays -0
+            const float a = act == 2 ? (u < 0.f ? 0.f : u) : act_fwd(u, act);
+            o[j] = (bf16)(a + (res ? (float)r[j] : 0.f));
         }
         *reinterpret_cast<bf16x8*>(y + m * ld_y + g * 8) = o;
     }
@@ -102,7 +104,12 @@ __global__ __launch_bounds__(256) void decode_eval_kernel(float* out, int B, int
         if (c == 0) v = (t + (float)(hw % W)) * s;
         else if (c == 1) v = (t + (float)(hw / W)) * s;
         else if (c < 26) v = expf(t) * s;
-        else v = 1.0f / (1.0f + expf(-t));
+        else {
+            // below t = -88.72 expf(-t) is inf and the quotient 0, where the sigmoid is a denormal number: exp(t) itself.  Every
+            // other t keeps the quotient's bits.
+            const float e = expf(-t);
+            v = e == INFINITY ? expf(t) : 1.0f / (1.0f + e);
+        }
         *p = v;
     }
 }
@@ -200,6 +207,7 @@ extern "C" int ep24_bn_act_infer(const void* z, int64_t ld_z, const float* gamma
     EP24_REQUIRE(z && gamma && beta && running_mean && running_var && y, EP24_E_ARG, "bn_act_infer: null pointer");
     EP24_REQUIRE(C % 8 == 0 && ld_z % 8 == 0 && ld_y % 8 == 0 && (!residual || ld_res % 8 == 0) && M > 0, EP24_E_ARG,
                  "bn_act_infer: C=%d / strides must be multiples of 8", C);
+    EP24_REQUIRE(C > 0 && C <= 8192, EP24_E_ARG, "bn_act_infer: C=%d must be in [8, 8192] (scale and shift take 2*C*4 bytes of the 64 KiB of LDS)", C);
     long blocks = (M * (C / 8) + 511) / 512;
     hipLaunchKernelGGL(bn_act_infer_kernel, dim3((unsigned)(blocks > 2048 ? 2048 : blocks)), dim3(256), 2 * C * sizeof(float), S_,
                        (const bf16*)z, ld_z, gamma, beta, running_mean, running_var, (bf16*)y, ld_y, (const bf16*)residual, ld_res, (long)M,
@@ -210,8 +218,8 @@ extern "C" int ep24_bn_act_infer(const void* z, int64_t ld_z, const float* gamma
 
 extern "C" int ep24_fold_bn(const float* flat, const float* bstat, const int64_t* desc, const int64_t* prefix, const int64_t* cprefix,
                             const float* eps, int n_seg, int64_t total, int64_t total_channels, void* w_folded, float* bias, void* stream) {
-    EP24_REQUIRE(flat && bstat && desc && prefix && cprefix && eps && w_folded && bias && n_seg > 0 && total > 0, EP24_E_ARG,
-                 "fold_bn: bad arguments");
+    EP24_REQUIRE(flat && bstat && desc && prefix && cprefix && eps && w_folded && bias && n_seg > 0 && total > 0 && total_channels > 0,
+                 EP24_E_ARG, "fold_bn: bad arguments");
     long blocks = (total + 1023) / 1024;
     hipLaunchKernelGGL(fold_bn_weights_kernel, dim3((unsigned)(blocks > 8192 ? 8192 : blocks)), dim3(256), 0, (hipStream_t)stream, flat, bstat,
                        (const long*)desc, (const long*)prefix, eps, n_seg, (bf16*)w_folded);

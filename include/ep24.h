@@ -565,7 +565,9 @@ int ep24_sector_labels(const double* rows, const double* geo, const double* rot,
  * N3  inference path: eval-mode network + postprocess
  * ------------------------------------------------------------------------------------------------ */
 /* BaseConv in eval mode (network_blocks.py:50-51 with BatchNorm2d.eval()): y = act(z*scale + shift) (+ residual),
- * scale = gamma / sqrt(running_var + eps), shift = beta - running_mean*scale. */
+ * scale = gamma / sqrt(running_var + eps), shift = beta - running_mean*scale.  C, ld_z, ld_y (and ld_res with a residual) are
+ * multiples of 8, M > 0 and 8 <= C <= 8192: the kernel keeps scale and shift in 2*C*4 bytes of LDS, 64 KiB at the most.
+ * Anything else is EP24_E_ARG before a launch. */
 int ep24_bn_act_infer(const void* z, int64_t ld_z, const float* gamma, const float* beta, const float* running_mean,
                       const float* running_var, void* y, int64_t ld_y, const void* residual, int64_t ld_res,
                       int64_t M, int C, float eps, int act, void* stream);
@@ -575,7 +577,8 @@ int ep24_head_decode_eval(float* out, int B, int A, int a0, int H, int W, float 
  * [Cout][T][Cin_pad]) and bias = beta - running_mean * scale.  flat = the fp32 parameter buffer, bstat = the running
  * statistics buffer; desc[n_seg][12] int64 = {master offset, packed offset, Cout, T, Cin, Cin_pad, gamma offset, beta offset
  * (flat), running-mean offset, running-var offset (bstat), bias offset, 0}; prefix / cprefix [n_seg+1] = element / channel
- * prefix sums; eps[n_seg]. */
+ * prefix sums; eps[n_seg].  Only the Cin real columns of a packed row are written.  n_seg, total = prefix[n_seg] and
+ * total_channels = cprefix[n_seg] are all > 0 (EP24_E_ARG otherwise, before a launch). */
 int ep24_fold_bn(const float* flat, const float* bstat, const int64_t* desc, const int64_t* prefix, const int64_t* cprefix,
                  const float* eps, int n_seg, int64_t total, int64_t total_channels, void* w_folded, float* bias, void* stream);
 /* conv -> BN(running statistics) -> act (+ residual) of the eval-mode network as ONE launch: the conv over the folded weights
@@ -588,7 +591,11 @@ int ep24_conv_fwd_infer_bf16(const void* x, int64_t ld_x, const void* w, const f
  * theta*cos(theta) factors, passed in as the host computes them).  nms: per image (one workgroup) candidates sorted by score (ties: lower row first), greedy
  * suppression of IoU > nms_thre within a class (torchvision batched_nms) or across classes (class_agnostic); keep
  * [B][A] receives the kept rows in order, keep_count[B] their number; sort_key / sort_idx / dead are [B][P] scratch,
- * P a power of two >= A.  gather: det[n][29] = (pred[:, :27], class_conf, class_pred) of one image's kept rows. */
+ * P a power of two >= A.  gather: det[n][29] = (pred[:, :27], class_conf, class_pred) of one image's kept rows.
+ * A NaN score is no candidate (NaN >= conf_thre is false: the row gets -1).  A NaN class score is never greater than the running
+ * maximum, so it is passed over - except in class column 0, where the scan starts: a leading NaN stays, class 0 is reported
+ * with class_conf = NaN and the row is no candidate.  The rectangle is fminf / fmaxf over the 24 points: a NaN point is left out.
+ * sort_key / sort_idx / dead need no initialisation; keep beyond keep_count is not written. */
 int ep24_post_prepare(const float* pred, int ncols, int num_classes, int64_t n_rows, float conf_thre,
                       const float* ray_factors /* [48]: theta_k*cos(theta_k), then theta_k*sin(theta_k) */, float* score,
                       float* conf, int32_t* cls, float* rect, void* stream);
