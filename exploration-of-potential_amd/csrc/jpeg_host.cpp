@@ -10,7 +10,10 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <vector>
+
 #include "../../include/ep24_jpeg.h"
+#include "jpeg_huff_core.h"
 
 namespace {
 
@@ -33,6 +36,7 @@ enum { LOOK = 9 };
 struct Huff {
     bool defined;
     int nvals;
+    uint8_t bits[16];              // codes per length 1 .. 16, as the file gives them
     uint8_t vals[256];
     uint16_t look[1 << LOOK];      // (length << 8) | symbol for codes of at most LOOK bits, 0 otherwise
     int32_t maxcode[17];           // largest code of each length, -1: none
@@ -50,6 +54,7 @@ struct Parsed {
 int build_huff(Huff& h, const uint8_t* bits, const uint8_t* vals, int nvals) {
     h.defined = true;
     h.nvals = nvals;
+    memcpy(h.bits, bits, 16);
     memcpy(h.vals, vals, (size_t)nvals);
     memset(h.look, 0, sizeof(h.look));
     int32_t code = 0;
@@ -632,5 +637,216 @@ extern "C" int ep24jpeg_entropy_decode(const uint8_t* bytes, int64_t n, int16_t*
                     }
             }
         }
+    return EP24JPEG_OK;
+}
+
+// ---- the device decoder's host side: the marker walk without Huffman work, and the kernel's phases with threads as loops ----
+
+namespace {
+
+// the end of the restart segment that starts at p: the first FF that is not followed by 00 (or the end of the file)
+int64_t segment_end(const uint8_t* d, int64_t p, int64_t n) {
+    while (p < n) {
+        const uint8_t* q = (const uint8_t*)memchr(d + p, 0xFF, (size_t)(n - p));
+        if (!q) return n;
+        p = q - d;
+        if (p + 1 < n && d[p + 1] == 0) {
+            p += 2;
+            continue;
+        }
+        return p;
+    }
+    return n;
+}
+
+void spec_of(ep24jpeg_huff_spec& s, const Huff& h) {
+    memset(&s, 0, sizeof(s));
+    memcpy(s.counts, h.bits, 16);
+    memcpy(s.symbols, h.vals, (size_t)h.nvals);
+    s.nsymbols = h.nvals;
+}
+
+int scan_layout(const uint8_t* d, int64_t n, ep24jpeg_scan_info& I, int64_t* segs, int64_t cap) {
+    Parsed P;
+    const int rc = parse(d, n, P);
+    if (rc) return rc;
+    const ep24jpeg_header& h = P.hd;
+    memset(&I, 0, sizeof(I));
+    I.header = h;
+    I.mcus_x = P.mcus_x;
+    I.mcus_y = P.mcus_y;
+    I.blocks_per_mcu = 0;
+    for (int c = 0; c < h.ncomp; ++c) {
+        I.blocks_per_mcu += h.h[c] * h.v[c];
+        spec_of(I.dc[c], P.dc[P.td[c]]);
+        spec_of(I.ac[c], P.ac[P.ta[c]]);
+    }
+    const int64_t mcus = (int64_t)P.mcus_x * P.mcus_y;
+    const int64_t ri = h.restart_interval;
+    const int64_t nseg = ri ? (mcus + ri - 1) / ri : 1;
+    I.nseg = (int32_t)nseg;
+    I.scan_pos = P.scan_pos;
+    if (segs && cap < nseg)
+        return fail(EP24JPEG_E_ARG, "ep24jpeg_scan_layout: room for %lld restart segments, the file has %lld", (long long)cap, (long long)nseg);
+    int64_t p = P.scan_pos;
+    int rst = 0;
+    for (int64_t s = 0; s < nseg; ++s) {
+        const int64_t e = segment_end(d, p, n);
+        if (segs) {
+            segs[3 * s] = p - P.scan_pos;
+            segs[3 * s + 1] = e - p;
+            segs[3 * s + 2] = ri ? (s + 1 < nseg ? ri : mcus - ri * (nseg - 1)) : mcus;
+        }
+        I.scan_len = e - P.scan_pos;
+        if (s + 1 == nseg) break;
+        int64_t q = e;
+        while (q + 1 < n && d[q] == 0xFF && d[q + 1] == 0xFF) ++q;          // fill bytes
+        if (q + 1 >= n || d[q] != 0xFF || d[q + 1] != 0xD0 + rst)
+            return fail(EP24JPEG_E_DATA, "jpeg: RST%d expected before MCU %lld", rst, (long long)((s + 1) * ri));
+        rst = (rst + 1) & 7;
+        p = q + 2;
+    }
+    return EP24JPEG_OK;
+}
+
+inline bool same(const ep24huff_state& a, const ep24huff_state& b) { return a.pos == b.pos && a.kj == b.kj; }
+
+}  // namespace
+
+extern "C" int ep24jpeg_scan_layout(const uint8_t* bytes, int64_t n, ep24jpeg_scan_info* info, int64_t* segments, int64_t seg_capacity) {
+    if (!bytes || !info || n < 0 || seg_capacity < 0) return fail(EP24JPEG_E_ARG, "ep24jpeg_scan_layout: null pointer or negative length");
+    return scan_layout(bytes, n, *info, segments, seg_capacity);
+}
+
+extern "C" int ep24jpeg_selfsync_emulate(const uint8_t* bytes, int64_t n, int subseq_bytes, int tile, int16_t* coef_out, int64_t capacity,
+                                         int32_t* rounds_out) {
+    if (!bytes || !coef_out || n < 0) return fail(EP24JPEG_E_ARG, "ep24jpeg_selfsync_emulate: null pointer or negative length");
+    const int S = subseq_bytes;
+    if ((S != 16 && S != 32 && S != 64 && S != 128 && S != 256) || tile < 1 || tile > 1024)
+        return fail(EP24JPEG_E_ARG, "ep24jpeg_selfsync_emulate: subsequences of %d bytes (16, 32, 64, 128 or 256) in tiles of %d (1 .. 1024)", S, tile);
+    if (rounds_out) *rounds_out = 0;
+    ep24jpeg_scan_info I;
+    int rc = scan_layout(bytes, n, I, nullptr, 0);
+    if (rc) return rc;
+    std::vector<int64_t> segs((size_t)I.nseg * 3);
+    rc = scan_layout(bytes, n, I, segs.data(), I.nseg);
+    if (rc) return rc;
+    const ep24jpeg_header& h = I.header;
+    if (capacity < h.ncoef)
+        return fail(EP24JPEG_E_ARG, "ep24jpeg_selfsync_emulate: capacity %lld below the %lld coefficients of the file", (long long)capacity, (long long)h.ncoef);
+    if (I.scan_len >= EP24JPEG_MAX_SCAN)
+        return fail(EP24JPEG_E_UNSUPPORTED, "jpeg: a scan of %lld bytes is above the device decoder's %d", (long long)I.scan_len, EP24JPEG_MAX_SCAN);
+    memset(coef_out, 0, (size_t)h.ncoef * sizeof(int16_t));
+
+    // setup: the tables as the kernel stages them, the image's geometry
+    std::vector<ep24huff_table> tab(6);
+    ep24huff_image im;
+    im.d = bytes + I.scan_pos;
+    for (int c = 0; c < 3; ++c) {
+        const int cc = c < h.ncomp ? c : 0;
+        ep24huff_build(tab[c], I.dc[cc].counts, I.dc[cc].symbols, I.dc[cc].nsymbols);
+        ep24huff_build(tab[3 + c], I.ac[cc].counts, I.ac[cc].symbols, I.ac[cc].nsymbols);
+    }
+    im.tabs = tab.data();
+    im.ncomp = h.ncomp, im.h0 = h.h[0], im.v0 = h.v[0], im.mcus_x = I.mcus_x, im.bpm = I.blocks_per_mcu;
+    im.ncoef = h.ncoef;
+    int64_t comp_off[3] = {0, 0, 0};
+    for (int c = 1; c < h.ncomp; ++c) comp_off[c] = comp_off[c - 1] + 64 * h.nblocks[c - 1];
+    im.off1 = comp_off[1], im.off2 = comp_off[2];
+    // the segment table with its cumulative subsequence count, as ep24.jpeg.pack uploads it
+    const int nseg = I.nseg;
+    std::vector<ep24huff_segment> sg((size_t)nseg);
+    std::vector<int64_t> first((size_t)nseg + 1);
+    int64_t mcu = 0;
+    first[0] = 0;
+    for (int s = 0; s < nseg; ++s) {
+        sg[s].off = (uint32_t)segs[3 * s];
+        sg[s].end = (uint32_t)(segs[3 * s] + segs[3 * s + 1]);
+        sg[s].first_mcu = (int32_t)mcu;
+        sg[s].expect = (int32_t)(segs[3 * s + 2] * im.bpm);
+        mcu += segs[3 * s + 2];
+        const int64_t ns = (segs[3 * s + 1] + S - 1) / S;
+        first[s + 1] = first[s] + (ns < 1 ? 1 : ns);
+    }
+    const int64_t total = first[nseg];
+
+    std::vector<ep24huff_state> start((size_t)tile), end((size_t)tile), prev((size_t)tile);
+    std::vector<int> begun((size_t)tile), incl((size_t)tile), seg_of((size_t)tile);
+    ep24huff_state carry = {0, 0};
+    int carry_blocks = 0, status = 0, max_rounds = 0;
+    int s_hint = 0;
+    for (int64_t t0 = 0; t0 < total; t0 += tile) {
+        const int act = (int)(total - t0 < tile ? total - t0 : tile);
+        // round 0: every thread from its anchored, carried or speculative start
+        for (int i = 0; i < act; ++i) {
+            const int64_t g = t0 + i;
+            while (first[s_hint + 1] <= g) ++s_hint;
+            const int s = s_hint;
+            seg_of[i] = s;
+            const int64_t li = g - first[s];
+            if (li == 0) start[i] = ep24huff_state{sg[s].off * 8u, 0};
+            else if (i == 0) start[i] = carry;
+            else start[i] = ep24huff_state{ep24huff_spec_start(im.d, sg[s].off, sg[s].off + (uint32_t)(li * S)), 0};
+        }
+        auto bound_of = [&](int i) {
+            const int s = seg_of[i];
+            const int64_t li = t0 + i - first[s];
+            const int64_t b = (int64_t)sg[s].off + (li + 1) * S;
+            return (uint32_t)(b < sg[s].end ? b : sg[s].end);
+        };
+        for (int i = 0; i < act; ++i) ep24huff_run<false>(im, sg[seg_of[i]], start[i], bound_of(i), &end[i], &begun[i], nullptr, 0, false);
+        int rounds = 1;
+        for (int r = 1; r <= act; ++r) {
+            prev = end;                                   // what the threads read in front of the barrier
+            bool decoded = false, changed = false;
+            for (int i = 1; i < act; ++i) {
+                if (t0 + i == first[seg_of[i]]) continue;      // anchored
+                if (same(prev[i - 1], start[i])) continue;
+                start[i] = prev[i - 1];
+                const ep24huff_state was = end[i];
+                ep24huff_run<false>(im, sg[seg_of[i]], start[i], bound_of(i), &end[i], &begun[i], nullptr, 0, false);
+                decoded = true;
+                if (!same(was, end[i])) changed = true;
+            }
+            if (decoded) ++rounds;
+            if (!changed) break;
+        }
+        if (rounds > max_rounds) max_rounds = rounds;
+        // the exclusive scan of the blocks begun, restarted at every segment, and the write pass
+        int run = 0;
+        for (int i = 0; i < act; ++i) run += begun[i], incl[i] = run;
+        int last_excl = 0;
+        for (int i = 0; i < act; ++i) {
+            const int s = seg_of[i];
+            const int64_t fs = first[s] > t0 ? first[s] : t0;
+            const int f = (int)(fs - t0);
+            const int excl = (incl[i] - begun[i]) - (incl[f] - begun[f]) + (first[s] < t0 ? carry_blocks : 0);
+            const bool last = t0 + i + 1 == first[s + 1];
+            if (ep24huff_run<true>(im, sg[s], start[i], bound_of(i), nullptr, nullptr, coef_out, excl, last)) status = EP24JPEG_E_DATA;
+            last_excl = excl;
+        }
+        carry = end[act - 1];
+        carry_blocks = last_excl + begun[act - 1];
+    }
+    // the DC pass: differences -> values per component in scan order, from zero at every restart segment
+    for (int c = 0; c < h.ncomp; ++c) {
+        const int hc = c ? 1 : im.h0, vc = c ? 1 : im.v0, hv = hc * vc;
+        const int64_t nq = (int64_t)I.mcus_x * I.mcus_y * hv;
+        const int64_t ri = h.restart_interval;
+        int32_t sum = 0;
+        for (int64_t q = 0; q < nq; ++q) {
+            const int64_t m = q / hv;
+            const int r = (int)(q - m * hv);
+            if (r == 0 && (ri ? m % ri == 0 : m == 0)) sum = 0;
+            const int64_t my = m / I.mcus_x, mx = m - my * I.mcus_x;
+            const int by = r / hc, bx = r - by * hc;
+            int16_t* at = coef_out + comp_off[c] + ((my * vc + by) * ((int64_t)I.mcus_x * hc) + (mx * hc + bx)) * 64;
+            sum += *at;
+            if (sum < -32768 || sum > 32767) status = EP24JPEG_E_DATA;
+            *at = (int16_t)sum;
+        }
+    }
+    if (rounds_out) *rounds_out = max_rounds;
+    if (status) return fail(EP24JPEG_E_DATA, "jpeg: the device decoder's status word is set (invalid code, data ends early, or DC out of range)");
     return EP24JPEG_OK;
 }

@@ -516,8 +516,8 @@ class MosaicTransform(TrainTransform):
         if not self.enabled:
             return super().batch(images, targets, input_dim, out_images=out_images, out_labels=out_labels)
         _lib.require_gpu()
-        from .jpeg import finish_mixed
-        images = finish_mixed(images)                     # entropy-decoded JPEG files (ep24.jpeg.JpegCoefficients) -> uint8 BGR on the device
+        from .jpeg import finish_checked
+        images = finish_checked(images)                   # entropy-decoded JPEG files (ep24.jpeg.JpegCoefficients) -> uint8 BGR on the device
         params = self.sample([tuple(im.shape[:2]) for im in images], input_dim,
                              [np.asarray(t).size // 51 for t in targets])
         imgs, labs, counts = mosaic_batch(images, targets, params, input_dim, self.max_labels, out_images, out_labels,

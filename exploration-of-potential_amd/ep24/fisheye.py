@@ -96,8 +96,8 @@ class FisheyeTransform(TrainTransform):
         if self._dist is None:
             self._dist = Image_Distortion(self.device)
         thetas = self.sample(len(images))
-        from .jpeg import finish_mixed
-        images = finish_mixed(images, device=self.device)
+        from .jpeg import finish_checked
+        images = finish_checked(images, device=self.device)
         dev_imgs = [torch.as_tensor(np.ascontiguousarray(im) if isinstance(im, np.ndarray) else im).to(self.device) for im in images]
         warped = self._dist.distort_batch(dev_imgs, None, thetas, self.custom_rows)[0]
         imgs, _ = preproc_batch(warped, input_dim, device=self.device, out=out_images)

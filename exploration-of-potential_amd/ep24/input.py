@@ -10,6 +10,7 @@ import torch
 
 from . import _lib
 from ._lib import call, ptr, stream_ptr
+from .jpeg import JpegError, JpegScan, check_status, finish_checked, finish_mixed
 
 
 def letterbox_geometry(h, w, input_size):
@@ -112,9 +113,11 @@ class TrainTransform:
 
     def batch(self, images, targets, input_dim, out_images=None, out_labels=None):
         """``images``: uint8 [h,w,3] arrays / tensors of any sizes, or entropy-decoded JPEG files (``ep24.jpeg.JpegCoefficients``):
-        those are finished on the GPU first (``ep24.jpeg.finish``, BGR, on the stream this call runs on)."""
-        from .jpeg import finish_mixed
-        images = finish_mixed(images)
+        those are finished on the GPU first (``ep24.jpeg.finish``, BGR, on the stream this call runs on).  ``ep24.jpeg.JpegScan`` items
+        (Huffman stage on the GPU) are finished too and their status words read before the pixels are used: corrupt entropy-coded
+        data raises ``JpegError`` with the file's name (one host synchronisation, for such items only: ``DataPrefetcher`` finishes its
+        batches itself, hands over plain tensors and reads the words in ``next()``, so this call does not wait there)."""
+        images = finish_checked(images)
         if self.fisheye is not None:
             images = self.warp(images)
         imgs, rs = preproc_batch(images, input_dim, out=out_images)
@@ -130,7 +133,9 @@ class DataPrefetcher:
     """The reference's prefetcher (data/data_prefetcher.py): the next batch is prepared on a side stream while the
     current step runs; ``next()`` makes the compute stream wait for it.  ``loader`` yields either ready tensors
     ``(images, labels, info, ids)`` (as the reference's loader does) or raw batches ``(list of uint8 HWC images or of
-    ``ep24.jpeg.JpegCoefficients``, list of label rows, info, ids)`` - then ``transform.batch`` (upload + the two preproc launches) runs on the side stream too."""
+    ``ep24.jpeg.JpegCoefficients`` / ``ep24.jpeg.JpegScan``, list of label rows, info, ids)`` - then ``transform.batch`` (upload + the two preproc launches) runs on the side stream too.
+    A batch with ``JpegScan`` items (Huffman stage on the GPU) carries status words: ``next()`` reads them after its stream wait and
+    raises ``JpegError`` with the file's name for corrupt entropy-coded data."""
 
     def __init__(self, loader, input_size=(640, 640), transform=None):
         _lib.require_gpu()
@@ -142,6 +147,7 @@ class DataPrefetcher:
         # the event recorded on the compute stream when batch k - 1 was handed out (everything enqueued before it - the step that
         # consumed batch k - 2 - has then run).  No allocation and no record_stream per batch.
         self._bufs, self._k, self._events = [None, None, None], 0, []
+        self._status_host, self._next_status = [None, None, None], None
         # host seconds of this thread inside the loader (next(): dataset + collate) and inside the upload / letterbox enqueue; the
         # second one BLOCKS in the pageable copies until the device buffer of batch k - 2 is free, i.e. it is where a GPU-bound
         # loop waits for the GPU (profiles/r05_trainer_8sets.json), not host work
@@ -180,6 +186,20 @@ class DataPrefetcher:
                     self._bufs[slot] = b
                 if len(self._events) >= 2:
                     self.stream.wait_event(self._events[-2])
+                self._next_status = None
+                if any(isinstance(im, JpegScan) for im in images):
+                    # files whose Huffman stage runs on the GPU: finished here, so that their status words are at hand; the words
+                    # travel to a page-locked buffer behind the batch's work on this stream, and next() reads them there
+                    images = finish_mixed(images, device=torch.device("cuda", torch.cuda.current_device()))
+                    words, n_words = images.status, int(images.status.numel())
+                    host = self._status_host[slot]
+                    if host is None or host.numel() < n_words:
+                        host = self._status_host[slot] = torch.empty(max(n_words, 64), dtype=torch.int32).pin_memory()
+                    host[:n_words].copy_(words, non_blocking=True)
+                    ev = torch.cuda.Event()
+                    ev.record()
+                    self._next_status = (host[:n_words], ev, images.status_items)
+                    images = list(images)               # plain tensors: the transform must not read the words (a host wait) here
                 self.next_input, self.next_target = self.transform.batch(images, targets, self.input_size, out_images=b[0], out_labels=b[1])
                 self._owned = True
 
@@ -187,6 +207,16 @@ class DataPrefetcher:
         cur = torch.cuda.current_stream()
         cur.wait_stream(self.stream)
         inp, tgt = self.next_input, self.next_target
+        st, self._next_status = self._next_status, None
+        if st is not None and inp is not None:
+            # the status words of the batch's device-decoded files.  This is a HOST wait that other batches do not make: next() blocks
+            # until the side stream has run this batch's Huffman launches and the copy of the words behind them (work enqueued a whole
+            # step ago); it does not wait for the compute stream
+            st[1].synchronize()
+            try:
+                check_status(st[0].numpy(), st[2])
+            except JpegError as e:
+                raise JpegError(e.code, "%s - such files can be read with --jpeg-decoder pil (Pillow)" % e.message) from None
         if inp is not None and not self._owned:
             inp.record_stream(cur)
             tgt.record_stream(cur)

@@ -9,6 +9,12 @@ default (``cv2.imread``'s order, what ``ep24.input.preproc_batch`` is fed), RGB 
 12-bit and four-component files, other samplings than 4:4:4 / 4:2:2 / 4:2:0, several scans and sides above 8192 raise ``JpegError``
 with ``code == EP24_E_UNSUPPORTED``; corrupt files raise it with ``EP24JPEG_E_DATA``.
 
+The Huffman stage can run on the GPU as well ("JPEG decode: Huffman stage on the GPU"); a file then travels as its scan bytes:
+
+    item = scan(bytes)                     # host: the marker walk only (ep24jpeg_scan_layout) -> JpegScan, no GPU - loader processes
+    images = finish([item, ...])           # GPU: upload, memset, ep24_jpeg_huffman + ep24_jpeg_dc, then the two launches; .status
+    images = decode([bytes, ...], entropy="device")       # both, and one read of the status words: corrupt data raises JpegError
+
 The writer mirrors the reader:
 
     coefs = forward([image, ...])          # GPU: one descriptor upload, ep24_jpeg_sample + ep24_jpeg_fdct, one copy to the host
@@ -102,6 +108,57 @@ class JpegCoefficients:
         return self.header.shape
 
 
+class _HuffSpec(ctypes.Structure):
+    _fields_ = [("counts", ctypes.c_uint8 * 16), ("symbols", ctypes.c_uint8 * 256), ("nsymbols", ctypes.c_int32)]
+
+
+class _ScanInfo(ctypes.Structure):
+    _fields_ = [("header", _Header), ("mcus_x", ctypes.c_int32), ("mcus_y", ctypes.c_int32), ("blocks_per_mcu", ctypes.c_int32),
+                ("nseg", ctypes.c_int32), ("scan_pos", ctypes.c_int64), ("scan_len", ctypes.c_int64), ("dc", _HuffSpec * 3), ("ac", _HuffSpec * 3)]
+
+
+SPEC_BYTES = ctypes.sizeof(_HuffSpec)                      # 276: what ep24_jpeg_huffman reads per table
+SUBSEQ_SIZES = (16, 32, 64, 128, 256)
+SUBSEQ_BYTES, TILE = 128, 1024                            # the device decoder's defaults: bytes per subsequence, subsequences per tile
+MAX_SCAN = 1 << 28
+
+
+class JpegScan:
+    """One file whose Huffman coding is still to be undone - on the device (``finish`` / ``decode(entropy="device")``): ``header``,
+    ``data`` (uint8: the entropy-coded bytes of the one scan, restart markers included), ``tables`` (uint8 [6, 276]: the DC tables of
+    component 0 .. 2, then the AC tables, as the file specifies them: 16 counts, 256 symbols, int32 count) and ``segments`` (int32
+    [nseg, 3]: byte offset in ``data``, length, MCUs of every restart segment).  Made by ``scan`` with the host library only.  Pickles
+    like JpegCoefficients; ``shape`` is the decoded image's (h, w, 3).  ``source``: a name for error messages (the dataset sets it)."""
+    __slots__ = ("header", "data", "tables", "segments", "mcus_x", "mcus_y", "tag", "source")
+
+    def __init__(self, header, data, tables, segments, mcus_x, mcus_y, tag=None, source=None):
+        self.header, self.data, self.tables, self.segments = header, data, tables, segments
+        self.mcus_x, self.mcus_y, self.tag, self.source = mcus_x, mcus_y, tag, source
+
+    def __getstate__(self):
+        import sys
+        data = self.data
+        if "torch" in sys.modules:                        # through shared memory between processes, as JpegCoefficients.coef
+            data = sys.modules["torch"].from_numpy(np.array(data, dtype=np.uint8))
+        return (self.header, data, self.tables, self.segments, self.mcus_x, self.mcus_y, self.tag, self.source)
+
+    def __setstate__(self, st):
+        self.header, data, self.tables, self.segments, self.mcus_x, self.mcus_y, self.tag, self.source = st
+        self.data = data if isinstance(data, np.ndarray) else data.numpy()
+
+    @property
+    def shape(self):
+        return self.header.shape
+
+
+class Finished(list):
+    """What ``finish`` / ``finish_mixed`` return when the batch held JpegScan items: the list of images, plus ``status`` (int32 device
+    tensor, one word per JpegScan item in batch order: 0 or EP24JPEG_E_DATA, valid once the stream has run) and ``status_items``
+    ((index in the batch, name) per word)."""
+    status = None
+    status_items = ()
+
+
 _host = None
 
 
@@ -126,6 +183,11 @@ def host_lib():
         L.ep24jpeg_entropy_encode.restype = ctypes.c_int
         L.ep24jpeg_entropy_encode.argtypes = [ctypes.POINTER(_Header), ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
                                               ctypes.POINTER(ctypes.c_int64)]
+        L.ep24jpeg_scan_layout.restype = ctypes.c_int
+        L.ep24jpeg_scan_layout.argtypes = [ctypes.c_char_p, ctypes.c_int64, ctypes.POINTER(_ScanInfo), ctypes.c_void_p, ctypes.c_int64]
+        L.ep24jpeg_selfsync_emulate.restype = ctypes.c_int
+        L.ep24jpeg_selfsync_emulate.argtypes = [ctypes.c_char_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64,
+                                                ctypes.POINTER(ctypes.c_int32)]
         if L.ep24jpeg_abi_version() != ABI_VERSION:
             raise Ep24Error("ep24: %s reports ABI version %d, ep24.jpeg expects %d - rebuild the library" %
                             (HOST_LIB_PATH, L.ep24jpeg_abi_version(), ABI_VERSION))
@@ -161,6 +223,37 @@ def entropy_decode(data, tag=None):
     return JpegCoefficients(hd, coef, tag)
 
 
+def scan(data, tag=None):
+    """-> JpegScan: the markers walked, no Huffman work (``ep24jpeg_scan_layout``).  Refuses what ``entropy_decode`` refuses in front of
+    the first coded bit, and a restart marker that is missing or out of sequence.  Uses the host library only."""
+    L, data, info = host_lib(), _bytes(data), _ScanInfo()
+    rc = L.ep24jpeg_scan_layout(data, len(data), ctypes.byref(info), None, 0)
+    if rc:
+        _raise(L, rc)
+    segs = np.empty((int(info.nseg), 3), dtype=np.int64)
+    rc = L.ep24jpeg_scan_layout(data, len(data), ctypes.byref(info), segs.ctypes.data, segs.shape[0])
+    if rc:
+        _raise(L, rc)
+    if info.scan_len >= MAX_SCAN:
+        raise JpegError(EP24_E_UNSUPPORTED, "scan: a scan of %d bytes is above the device decoder's %d" % (info.scan_len, MAX_SCAN))
+    tables = np.frombuffer(bytes(info.dc) + bytes(info.ac), dtype=np.uint8).reshape(6, SPEC_BYTES)
+    body = np.frombuffer(data, dtype=np.uint8, count=int(info.scan_len), offset=int(info.scan_pos))
+    return JpegScan(JpegHeader(info.header), body, tables, segs.astype(np.int32), int(info.mcus_x), int(info.mcus_y), tag)
+
+
+def selfsync_emulate(data, subseq_bytes=SUBSEQ_BYTES, tile=TILE):
+    """The device decoder's phases on the host (``ep24jpeg_selfsync_emulate``) -> (JpegCoefficients, the largest number of rounds a
+    tile needed).  For tests and tools; uses the host library only."""
+    L, data = host_lib(), _bytes(data)
+    hd = parse(data)
+    coef = np.empty(hd.ncoef, dtype=np.int16)
+    rounds = ctypes.c_int32(0)
+    rc = L.ep24jpeg_selfsync_emulate(data, len(data), int(subseq_bytes), int(tile), coef.ctypes.data, coef.size, ctypes.byref(rounds))
+    if rc:
+        _raise(L, rc)
+    return JpegCoefficients(hd, coef), int(rounds.value)
+
+
 def _mode(hd):
     if hd.ncomp == 1:
         return 0
@@ -179,11 +272,33 @@ def _check(it):
     for c in range(hd.ncomp):
         if hd.blocks_w[c] != mx * hd.h[c] or hd.blocks_h[c] != my * hd.v[c] or hd.nblocks[c] != hd.blocks_w[c] * hd.blocks_h[c]:
             raise JpegError(EP24_E_ARG, "finish: the block grid of component %d does not fit a %d x %d image" % (c, hd.width, hd.height))
+    if np.asarray(hd.qt).shape != (hd.ncomp, 64) or np.asarray(hd.qt).dtype != np.uint16:
+        raise JpegError(EP24_E_ARG, "finish: the quantisation tables must be uint16 [%d, 64]" % hd.ncomp)
+    if isinstance(it, JpegScan):
+        _check_scan(it, mx, my)
+        return
     coef = it.coef
     if not isinstance(coef, np.ndarray) or coef.dtype != np.int16 or coef.ndim != 1 or coef.size != 64 * sum(hd.nblocks) or coef.size != hd.ncoef:
         raise JpegError(EP24_E_ARG, "finish: the coefficient array does not hold the %d blocks of the header" % sum(hd.nblocks))
-    if np.asarray(hd.qt).shape != (hd.ncomp, 64) or np.asarray(hd.qt).dtype != np.uint16:
-        raise JpegError(EP24_E_ARG, "finish: the quantisation tables must be uint16 [%d, 64]" % hd.ncomp)
+
+
+def _check_scan(it, mx, my):
+    """What ep24_jpeg_huffman indexes with: the segment rows lie inside the bytes and hold the image's MCUs between them."""
+    hd, d, sg, tb = it.header, it.data, it.segments, it.tables
+    if hd.ncoef != 64 * sum(hd.nblocks) or (it.mcus_x, it.mcus_y) != (mx, my):
+        raise JpegError(EP24_E_ARG, "finish: the scan's MCU grid does not fit a %d x %d image" % (hd.width, hd.height))
+    if not isinstance(d, np.ndarray) or d.dtype != np.uint8 or d.ndim != 1 or d.size >= MAX_SCAN:
+        raise JpegError(EP24_E_ARG, "finish: the scan bytes must be a one-dimensional uint8 array below %d bytes" % MAX_SCAN)
+    if not isinstance(tb, np.ndarray) or tb.dtype != np.uint8 or tb.shape != (6, SPEC_BYTES):
+        raise JpegError(EP24_E_ARG, "finish: the table specifications must be uint8 [6, %d]" % SPEC_BYTES)
+    ok = isinstance(sg, np.ndarray) and sg.dtype == np.int32 and sg.ndim == 2 and sg.shape[1] == 3 and sg.shape[0] >= 1
+    if ok:
+        off, ln, mc = sg[:, 0].astype(np.int64), sg[:, 1].astype(np.int64), sg[:, 2].astype(np.int64)
+        ri = hd.restart_interval
+        ok = bool((off >= 0).all() and (ln >= 0).all() and (off + ln <= d.size).all() and (mc >= 1).all() and int(mc.sum()) == mx * my)
+        ok = ok and (len(sg) == (-(-mx * my // ri) if ri else 1)) and (not ri or bool((mc[:-1] == ri).all()))
+    if not ok:
+        raise JpegError(EP24_E_ARG, "finish: the segment table does not fit the scan's %d bytes and %d MCUs" % (d.size, mx * my))
 
 
 def _al(x, a):
@@ -194,26 +309,48 @@ class Packed:
     """A batch ready for upload: ``host`` (uint8: [coefficients | tables | plane descriptors | image descriptors], every part 16-byte
     aligned) and where the parts start; ``blocks`` / ``groups`` (IDCT blocks, 4-pixel groups of the colour kernel), ``out_bytes`` and
     ``shapes`` ((byte offset, h, w) of every image in the output buffer)."""
-    __slots__ = ("host", "o_qt", "o_pd", "o_id", "n_qt", "n_planes", "n_images", "blocks", "groups", "out_bytes", "shapes")
+    __slots__ = ("host", "o_qt", "o_pd", "o_id", "n_qt", "n_planes", "n_images", "blocks", "groups", "out_bytes", "shapes",
+                 "n_scan", "scan_items", "host_split", "gap", "dev_size", "o_hd", "o_sg", "n_seg", "o_tb", "o_by", "n_bytes",
+                 "subseq_bytes", "tile")
+
+    # With JpegScan items in the batch the DEVICE buffer has a part the host buffer lacks: the coefficients of those items, which the
+    # device decodes itself.  The planes of the JpegCoefficients items come first (``host_split`` bytes, uploaded), then the planes of
+    # the JpegScan items (``gap`` bytes, zeroed on the stream and filled by ep24_jpeg_huffman + ep24_jpeg_dc), then everything else:
+    # device offset = host offset + gap for all that lies behind the coefficients.  The o_* are DEVICE offsets.  Behind the image
+    # descriptors: o_hd (int64 [n_scan, 16]), o_sg (int32 [n_seg, 6]), o_tb (uint8 [n_scan, 6, 276]), o_by (the scans, each 16-byte
+    # aligned, n_bytes in all), as include/ep24.h describes them.  Without JpegScan items gap is 0 and the two buffers are one.
 
 
 _staging = {}        # finish()'s host buffer, kept and grown: a fresh 33 MB array per batch costs its page faults again (7.6 against 3.4 ms)
 
 
-def pack(items, staging=None):
-    """The host half of ``finish``: checks every item and builds the one buffer that is uploaded.  ``staging``: a dict that keeps the
-    host buffer between calls - ``host`` is then a view of it, valid until the next call with the same dict."""
+def pack(items, staging=None, subseq_bytes=None, tile=None):
+    """The host half of ``finish``: checks every item (JpegCoefficients or JpegScan) and builds the one buffer that is uploaded.
+    ``staging``: a dict that keeps the host buffer between calls - ``host`` is then a view of it, valid until the next call with the
+    same dict.  ``subseq_bytes`` / ``tile``: the device decoder's subsequence size and threads per workgroup (SUBSEQ_BYTES, TILE)."""
+    S, tile = int(subseq_bytes or SUBSEQ_BYTES), int(tile or TILE)
+    if S not in SUBSEQ_SIZES or not 64 <= tile <= 1024 or tile % 64:
+        raise JpegError(EP24_E_ARG, "pack: subsequences of %d bytes (one of %s) in tiles of %d (a multiple of 64 up to 1024)" % (S, SUBSEQ_SIZES, tile))
     pdesc, idesc, qts, shapes = [], [], [], []
     blocks = groups = out_off = 0
     for it in items:
         _check(it)
-        hd = it.header
-        first = []
+    # the planes of the JpegCoefficients items first, then those of the JpegScan items: one upload in front of the part the device fills
+    firsts, scan_items = {}, [i for i, it in enumerate(items) if isinstance(it, JpegScan)]
+    order = [i for i, it in enumerate(items) if not isinstance(it, JpegScan)] + scan_items
+    blocks_c = 0
+    for i in order:
+        hd = items[i].header
+        firsts[i] = []
         for c in range(hd.ncomp):
-            first.append(blocks)
+            firsts[i].append(blocks)
             pdesc.append([blocks, hd.blocks_w[c], len(qts), 0])
             qts.append(hd.qt[c])
             blocks += hd.nblocks[c]
+        if not isinstance(items[i], JpegScan):
+            blocks_c = blocks
+    for i, it in enumerate(items):
+        hd, first = it.header, firsts[i]
         H, W, mode = hd.height, hd.width, _mode(hd)
         dw = -(-W // 2) if mode >= 2 else W
         dh = -(-H // 2) if mode == 3 else H
@@ -234,37 +371,122 @@ def pack(items, staging=None):
     P.o_pd = _al(P.o_qt + qt.nbytes, 16)
     P.o_id = _al(P.o_pd + pd.nbytes, 16)
     size = P.o_id + idn.nbytes
+    P.n_scan, P.scan_items, P.subseq_bytes, P.tile = len(scan_items), scan_items, S, tile
+    P.host_split, P.gap = blocks_c * 128, (blocks - blocks_c) * 128
+    P.o_hd = P.o_sg = P.o_tb = P.o_by = P.n_seg = P.n_bytes = 0
+    if scan_items:
+        hdesc, srows, by_off, nseg = [], [], 0, 0
+        for i in scan_items:
+            it = items[i]
+            hd, sg = it.header, it.segments.astype(np.int64)
+            nsub = np.maximum(-(-sg[:, 1] // S), 1)
+            rows = np.zeros((len(sg), 6), dtype=np.int64)
+            rows[:, 0], rows[:, 1], rows[:, 3] = sg[:, 0], sg[:, 1], sg[:, 2]
+            rows[1:, 2] = np.cumsum(sg[:-1, 2])
+            rows[1:, 4] = np.cumsum(nsub[:-1])
+            srows.append(rows.astype(np.int32))
+            hdesc.append([by_off, it.data.size, nseg, len(sg), int(nsub.sum()), 64 * (firsts[i][0] - blocks_c), hd.ncoef, hd.ncomp,
+                          hd.h[0], hd.v[0], it.mcus_x, it.mcus_y, hd.restart_interval, 0, 0, 0])
+            nseg += len(sg)
+            by_off += _al(it.data.size, 16)
+        hdn = np.asarray(hdesc, dtype=np.int64).reshape(-1)
+        sgn = np.concatenate(srows).reshape(-1)
+        P.n_seg, P.n_bytes = nseg, max(by_off, 16)
+        P.o_hd = _al(size, 16)
+        P.o_sg = _al(P.o_hd + hdn.nbytes, 16)
+        P.o_tb = _al(P.o_sg + sgn.nbytes, 16)
+        P.o_by = _al(P.o_tb + len(scan_items) * 6 * SPEC_BYTES, 16)
+        size = P.o_by + P.n_bytes
+    P.dev_size = size
+    size -= P.gap                                         # the host buffer lacks the coefficients the device decodes itself
     if staging is None:
         host = np.empty(size, dtype=np.uint8)
     else:
         if staging.get("buf") is None or staging["buf"].size < size:
             staging["buf"] = np.empty(size + size // 4, dtype=np.uint8)
         host = staging["buf"][:size]
-    p = 0
+    p, g = 0, P.gap
     for it in items:
-        host[p:p + it.coef.nbytes] = it.coef.view(np.uint8)
-        p += it.coef.nbytes
-    host[P.o_qt:P.o_qt + qt.nbytes] = qt.view(np.uint8)
-    host[P.o_pd:P.o_pd + pd.nbytes] = pd.view(np.uint8)
-    host[P.o_id:P.o_id + idn.nbytes] = idn.view(np.uint8)
+        if not isinstance(it, JpegScan):
+            host[p:p + it.coef.nbytes] = it.coef.view(np.uint8)
+            p += it.coef.nbytes
+    host[P.o_qt - g:P.o_qt - g + qt.nbytes] = qt.view(np.uint8)
+    host[P.o_pd - g:P.o_pd - g + pd.nbytes] = pd.view(np.uint8)
+    host[P.o_id - g:P.o_id - g + idn.nbytes] = idn.view(np.uint8)
+    if scan_items:
+        host[P.o_hd - g:P.o_hd - g + hdn.nbytes] = hdn.view(np.uint8)
+        host[P.o_sg - g:P.o_sg - g + sgn.nbytes] = sgn.view(np.uint8)
+        p = P.o_tb - g
+        for i in scan_items:
+            host[p:p + 6 * SPEC_BYTES] = items[i].tables.reshape(-1)
+            p += 6 * SPEC_BYTES
+        p = P.o_by - g
+        for i in scan_items:
+            d = items[i].data
+            host[p:p + d.size] = d
+            p += _al(d.size, 16)
     P.host, P.n_qt, P.n_planes, P.n_images = host, len(qts), len(pdesc) - 1, len(items)
     P.blocks, P.groups, P.out_bytes, P.shapes = blocks, groups, out_off, shapes
     return P
 
 
-def launch(P, buf, planes, out, bgr=True):
-    """The two launches on the current stream.  buf: ``P.host`` on the device; planes: uint8 [64 * P.blocks]; out: uint8 [P.out_bytes]."""
+def upload(P, dev):
+    """``P.host`` -> the device buffer the launches read (uint8 [P.dev_size]) on the current stream: one copy, or - with both kinds of
+    items in the batch - one in front of the coefficients the device decodes itself and one behind them."""
+    import torch
+    # a copy from pageable memory has left the host buffer when the call returns (the runtime stages it), as ep24.input relies on
+    # for the temporaries it uploads: the buffer is free for the next batch
+    host = torch.from_numpy(P.host)
+    if not P.gap:
+        return host.to(dev, non_blocking=True)
+    buf = torch.empty(P.dev_size, dtype=torch.uint8, device=dev)
+    if P.host_split:
+        buf[:P.host_split].copy_(host[:P.host_split], non_blocking=True)
+    buf[P.host_split + P.gap:].copy_(host[P.host_split:], non_blocking=True)
+    return buf
+
+
+def launch_entropy(P, buf, status):
+    """The device Huffman stage of the batch's JpegScan items on the current stream: the memset of their coefficients, ep24_jpeg_huffman,
+    ep24_jpeg_dc.  buf: what ``upload`` returned; status: int32 [P.n_scan] on the device."""
     from . import _lib
-    if buf.numel() != P.host.size or planes.numel() < 64 * P.blocks or out.numel() < P.out_bytes:
+    if buf.numel() != P.dev_size or status.numel() < P.n_scan:
         raise JpegError(EP24_E_ARG, "launch: buffers smaller than the packed batch needs")
+    base, s = buf.data_ptr(), _lib.stream_ptr()
+    coef = base + P.host_split
+    buf[P.host_split:P.host_split + P.gap].zero_()
+    _lib.call("jpeg_huffman", base + P.o_by, P.n_bytes, base + P.o_hd, P.n_scan, base + P.o_sg, P.n_seg, base + P.o_tb, P.subseq_bytes, P.tile,
+              coef, P.gap // 2, _lib.ptr(status), s)
+    _lib.call("jpeg_dc", base + P.o_hd, P.n_scan, coef, P.gap // 2, _lib.ptr(status), s)
+
+
+def launch(P, buf, planes, out, bgr=True, status=None):
+    """The launches on the current stream.  buf: ``P.host`` on the device (``upload``); planes: uint8 [64 * P.blocks]; out: uint8
+    [P.out_bytes]; status: int32 [P.n_scan], needed when the batch holds JpegScan items (three more launches in front)."""
+    from . import _lib
+    if buf.numel() != P.dev_size or planes.numel() < 64 * P.blocks or out.numel() < P.out_bytes:
+        raise JpegError(EP24_E_ARG, "launch: buffers smaller than the packed batch needs")
+    if P.n_scan:
+        if status is None:
+            raise JpegError(EP24_E_ARG, "launch: a batch with JpegScan items needs its status words")
+        launch_entropy(P, buf, status)
     base, s = buf.data_ptr(), _lib.stream_ptr()
     _lib.call("jpeg_idct", base, base + P.o_qt, P.n_qt, base + P.o_pd, P.n_planes, P.blocks, _lib.ptr(planes), s)
     _lib.call("jpeg_color", _lib.ptr(planes), base + P.o_id, P.n_images, P.groups, _lib.ptr(out), P.out_bytes, 1 if bgr else 0, s)
 
 
-def finish(items, device="cuda:0", bgr=True):
-    """items: list of JpegCoefficients -> list of uint8 [h, w, 3] device tensors (views of one buffer).  One concatenated upload
-    (coefficients, tables, descriptors), two launches on the current stream, no host synchronisation."""
+def _name(it, i):
+    src = getattr(it, "source", None)
+    if src is not None:
+        return str(src)
+    return "item %d" % i if it.tag is None else "item %d (%r)" % (i, it.tag)
+
+
+def finish(items, device="cuda:0", bgr=True, subseq_bytes=None, tile=None):
+    """items: list of JpegCoefficients and / or JpegScan -> list of uint8 [h, w, 3] device tensors (views of one buffer).  One
+    concatenated upload (coefficients, tables, descriptors; for JpegScan items their scan bytes instead of coefficients), two launches
+    on the current stream - with JpegScan items the memset of their coefficients, ep24_jpeg_huffman and ep24_jpeg_dc in front, and the
+    result is a ``Finished`` list that carries their status words.  No host synchronisation."""
     from . import _lib
     _lib.require_gpu()
     items = list(items)
@@ -272,20 +494,66 @@ def finish(items, device="cuda:0", bgr=True):
         return []
     import torch
     dev = torch.device(device)
-    P = pack(items, _staging)
-    # a copy from pageable memory has left the host buffer when the call returns (the runtime stages it), as ep24.input relies on
-    # for the temporaries it uploads: the buffer is free for the next batch
-    buf = torch.from_numpy(P.host).to(dev, non_blocking=True)
+    P = pack(items, _staging, subseq_bytes, tile)
+    buf = upload(P, dev)
     planes = torch.empty(P.blocks * 64, dtype=torch.uint8, device=dev)
     out = torch.empty(P.out_bytes, dtype=torch.uint8, device=dev)
-    launch(P, buf, planes, out, bgr)
+    status = torch.empty(P.n_scan, dtype=torch.int32, device=dev) if P.n_scan else None
+    launch(P, buf, planes, out, bgr, status)
     # buf and planes go back to the caching allocator on return: it hands a block out again to work of this stream only
-    return [out[o:o + h * w * 3].view(h, w, 3) for o, h, w in P.shapes]
+    images = [out[o:o + h * w * 3].view(h, w, 3) for o, h, w in P.shapes]
+    if not P.n_scan:
+        return images
+    images = Finished(images)
+    images.status, images.status_items = status, [(i, _name(items[i], i)) for i in P.scan_items]
+    return images
 
 
-def decode(datas, device="cuda:0", bgr=True):
-    """list of JPEG files as bytes -> list of uint8 [h, w, 3] device tensors: ``entropy_decode`` of each, then one ``finish``."""
-    return finish([entropy_decode(d) for d in datas], device=device, bgr=bgr)
+def check_status(status, status_items):
+    """Raises JpegError(EP24JPEG_E_DATA) for the first item whose status word is set.  status: the words on the host (any sequence)."""
+    for code, (i, name) in zip([int(c) for c in status], status_items):
+        if code:
+            raise JpegError(EP24JPEG_E_DATA if code == EP24JPEG_E_DATA else code,
+                            "%s: the device decoder found corrupt or truncated entropy-coded data (status %d)" % (name, code))
+
+
+def entropy_decode_device(datas, device="cuda:0", subseq_bytes=None, tile=None):
+    """list of JPEG files as bytes -> list of int16 numpy arrays in ``entropy_decode``'s layout, decoded by ep24_jpeg_huffman +
+    ep24_jpeg_dc; the list carries ``status`` (numpy int32, one word per file) and raises nothing for a set word.  For tests and
+    tools: it copies the coefficients back, which the product never does."""
+    from . import _lib
+    _lib.require_gpu()
+    items = [d if isinstance(d, JpegScan) else scan(d) for d in datas]
+    out = Finished()
+    if not items:
+        return out
+    import torch
+    dev = torch.device(device)
+    P = pack(items, None, subseq_bytes, tile)
+    buf = upload(P, dev)
+    status = torch.empty(P.n_scan, dtype=torch.int32, device=dev)
+    launch_entropy(P, buf, status)
+    flat = buf[:P.gap].cpu().numpy().view(np.int16)
+    p = 0
+    for it in items:
+        out.append(flat[p:p + it.header.ncoef])
+        p += it.header.ncoef
+    out.status, out.status_items = status.cpu().numpy(), [(i, _name(it, i)) for i, it in enumerate(items)]
+    return out
+
+
+def decode(datas, device="cuda:0", bgr=True, entropy="host"):
+    """list of JPEG files as bytes -> list of uint8 [h, w, 3] device tensors.  ``entropy="host"``: ``entropy_decode`` of each, then one
+    ``finish``.  ``entropy="device"``: ``scan`` of each, one ``finish`` that undoes the Huffman coding on the GPU too, then ONE read
+    of the status words: JpegError(EP24JPEG_E_DATA) names the first corrupt item."""
+    if entropy not in ("host", "device"):
+        raise JpegError(EP24_E_ARG, "decode: entropy must be 'host' or 'device', got %r" % (entropy,))
+    if entropy == "host":
+        return finish([entropy_decode(d) for d in datas], device=device, bgr=bgr)
+    out = finish([scan(d) for d in datas], device=device, bgr=bgr)
+    if out:
+        check_status(out.status.cpu().numpy(), out.status_items)
+    return list(out)
 
 
 # ---- the writer ----
@@ -447,17 +715,39 @@ def encode(images, quality=95, subsampling="4:2:0", bgr=True, restart_interval=0
     return [entropy_encode(c) for c in forward(images, quality, subsampling, bgr, restart_interval)]
 
 
+def finish_checked(images, device="cuda:0", bgr=True):
+    """``finish_mixed`` for a caller that uses the pixels at once and keeps no status words (the transforms' ``batch``): with JpegScan
+    items in the batch it reads their status words - one host synchronisation - and raises JpegError(EP24JPEG_E_DATA) with the item's
+    name and the pointer to ``--jpeg-decoder pil``, so that no corrupt file is ever used as pixels.  Only a batch that THIS call
+    finishes is checked: a ``Finished`` list that comes in belongs to whoever finished it (``DataPrefetcher`` hands the transform a
+    plain list and reads the words itself a step later) and passes without a synchronisation; without JpegScan items this is
+    ``finish_mixed``."""
+    own = any(isinstance(im, JpegScan) for im in images)
+    out = finish_mixed(images, device=device, bgr=bgr)
+    if own and isinstance(out, Finished):
+        try:
+            check_status(out.status.cpu().numpy(), out.status_items)
+        except JpegError as e:
+            raise JpegError(e.code, "%s - such files can be read with --jpeg-decoder pil (Pillow)" % e.message) from None
+        out = list(out)
+    return out
+
+
 def is_coefficients(x):
     return isinstance(x, JpegCoefficients)
 
 
 def finish_mixed(images, device="cuda:0", bgr=True):
-    """A batch in which some (or all, or none) of the images are JpegCoefficients: those are finished in ONE call, the others pass."""
-    idx = [i for i, im in enumerate(images) if isinstance(im, JpegCoefficients)]
+    """A batch in which some (or all, or none) of the images are JpegCoefficients or JpegScan: those are finished in ONE call, the
+    others pass.  With JpegScan items the result is a ``Finished`` list: ``status`` and ``status_items`` (indices in THIS batch)."""
+    idx = [i for i, im in enumerate(images) if isinstance(im, (JpegCoefficients, JpegScan))]
     if not idx:
         return images
     done = finish([images[i] for i in idx], device=device, bgr=bgr)
-    images = list(images)
+    items, images = images, list(images)
     for i, t in zip(idx, done):
         images[i] = t
+    if isinstance(done, Finished):
+        images = Finished(images)
+        images.status, images.status_items = done.status, [(idx[j], _name(items[idx[j]], idx[j])) for j, _ in done.status_items]
     return images

@@ -6,7 +6,9 @@ Every ``*.txt`` of ``label_dir`` is one item; its image is ``<stem>.jpg`` in ``d
 is not a number.  Items are ``(image, rows [k, 51], (h, w), id)`` and are collated by ``raw_collate``.  With ``decoder="gpu"`` the
 image is an ``ep24.jpeg.JpegCoefficients``: the loader process runs the Huffman stage only (host library, no GPU, no ``libep24.so``)
 and ``TrainTransform.batch`` / ``MosaicTransform.batch`` finish the decode on the GPU.  ``decoder="pil"`` hands over Pillow's decode
-as a uint8 HWC BGR array instead - for files the native path refuses (progressive, CMYK, ...).
+as a uint8 HWC BGR array instead - for files the native path refuses (progressive, CMYK, ...).  With ``decoder="device"`` the image
+is an ``ep24.jpeg.JpegScan``: the loader process only walks the markers and hands over the scan's bytes, the Huffman stage runs on
+the GPU too; what the marker walk cannot see (corrupt entropy-coded data) is reported by ``DataPrefetcher.next()`` with the file's name.
 
 ``img_info`` is the TRUE ``(h, w)``: the reference returns ``(h, h)`` (coco24p.py:57, ``img.shape[0], img.shape[0]``), which is
 wrong for every image that is not square; nothing downstream of it in the reference's trainer reads the second value.
@@ -21,8 +23,8 @@ from ep24 import jpeg, labels24
 
 class COCO24PFolderDataset(torch.utils.data.Dataset):
     def __init__(self, data_dir, label_dir, decoder="gpu", report_cuda=False):
-        if decoder not in ("gpu", "pil"):
-            raise ValueError("COCO24PFolderDataset: decoder must be 'gpu' or 'pil', got %r" % (decoder,))
+        if decoder not in ("gpu", "pil", "device"):
+            raise ValueError("COCO24PFolderDataset: decoder must be 'gpu', 'pil' or 'device', got %r" % (decoder,))
         if decoder == "pil":
             try:
                 import PIL.Image  # noqa: F401
@@ -67,6 +69,10 @@ class COCO24PFolderDataset(torch.utils.data.Dataset):
             return np.ascontiguousarray(rgb[:, :, ::-1])                         # BGR, as cv2.imread returns it
         try:
             tag = torch.cuda.is_initialized() if self.report_cuda else None
+            if self.decoder == "device":
+                item = jpeg.scan(data, tag=tag)
+                item.source = path                        # a corrupt scan shows only on the GPU: the prefetcher names the file
+                return item
             return jpeg.entropy_decode(data, tag=tag)
         except jpeg.JpegError as e:
             raise jpeg.JpegError(e.code, "%s: %s - such files can be read with --jpeg-decoder pil (Pillow)" % (path, e.message)) from None

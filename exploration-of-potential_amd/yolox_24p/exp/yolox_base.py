@@ -33,7 +33,8 @@ class Exp(BaseExp):
         self.label_dir = None
         self.val_data_dir = None
         self.val_label_dir = None
-        self.jpeg_decoder = "gpu"        # "gpu": Huffman stage in the loader processes, the rest on the GPU (ep24.jpeg); "pil": Pillow
+        self.jpeg_decoder = "gpu"        # "gpu": Huffman stage in the loader processes, the rest on the GPU (ep24.jpeg); "pil": Pillow;
+        #                                  "device": the loader processes only walk the markers, the Huffman stage runs on the GPU too
         self.data_seed = 0               # seed of the per-epoch shuffle of the folder dataset
         # augmentation (stock YOLOX's names and values; read by train_24p.py --augment only: ep24.augment.MosaicTransform)
         self.mosaic_prob = 1.0

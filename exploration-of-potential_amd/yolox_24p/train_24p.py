@@ -498,8 +498,9 @@ def make_parser():
     p.add_argument("--label-dir", default=None, type=str, help="folder of COCO_24p_label/<stem>.txt files (labels_create_24p.py writes them)")
     p.add_argument("--val-data-dir", default=None, type=str, help="folder of validation images (with --val-label-dir) for --eval-interval")
     p.add_argument("--val-label-dir", default=None, type=str, help="folder of validation label files")
-    p.add_argument("--jpeg-decoder", default=None, choices=["gpu", "pil"], help="gpu (default): ep24.jpeg; pil: Pillow's decode in the loader "
-                   "processes, for files the native path refuses (progressive, CMYK, 12-bit)")
+    p.add_argument("--jpeg-decoder", default=None, choices=["gpu", "pil", "device"], help="gpu (default): ep24.jpeg; pil: Pillow's decode in the "
+                   "loader processes, for files the native path refuses (progressive, CMYK, 12-bit); device: as gpu, with the Huffman stage on "
+                   "the GPU too (the loader processes hand over the scan bytes; a corrupt file is reported when its batch is handed out)")
     p.add_argument("--output-dir", default=None, type=str, help="overrides exp.output_dir")
     p.add_argument("--synthetic-len", default=0, type=int, help="images per synthetic epoch (overrides exp.synthetic_len; a checkpoint is written per epoch)")
     p.add_argument("--steps", default=0, type=int, help="stop after this many steps (0 = run all epochs)")

@@ -955,6 +955,32 @@ int ep24_jpeg_idct(const void* coef, const void* qt, int nqt, const int64_t* pla
 int ep24_jpeg_color(const uint8_t* planes, const int64_t* image_desc, int n, int64_t total_groups, uint8_t* out, int64_t out_bytes,
                     int bgr, void* stream);
 
+/* Baseline JPEG decode, the Huffman stage on the device ("JPEG decode: Huffman stage on the GPU"): the scan bytes of a batch
+ * of files -> int16 coefficients in ep24_jpeg_idct's layout, by self-synchronising subsequence decoders; the marker walk that makes the
+ * inputs is ep24jpeg_scan_layout of libep24jpeg.so (include/ep24_jpeg.h), the state machine is csrc/jpeg_huff_core.h.
+ * ep24_jpeg_huffman: bytes[nbytes] = the entropy-coded data of all images; image_desc[n][16] int64 = {0 byte offset of the image's scan
+ *   in bytes, 1 its length (below 2^28), 2 first row of the image in segments, 3 its restart segments (>= 1), 4 its subsequences (the sum
+ *   of max(1, ceil(length / subseq_bytes)) over its segments), 5 first coefficient of the image in coef, 6 its coefficient count, 7
+ *   components (1 or 3), 8 / 9 luma sampling h / v (1 or 2; chroma is 1 x 1), 10 / 11 MCUs per row / MCU rows, 12 restart interval in
+ *   MCUs (0: none), 13 .. 15 0}; segments[nseg][6] int32 = {byte offset relative to the image's scan, length, first MCU, MCUs the
+ *   segment must hold, first subsequence of the segment within the image (cumulative, segment 0: 0), 0}; table_specs[n][6] records of 276
+ *   bytes (ep24jpeg_huff_spec: 16 code counts, 256 symbols, int32 symbol count): DC of component 0 .. 2, then AC of component 0 .. 2.
+ *   subseq_bytes: 16, 32, 64, 128 or 256; tile: threads per workgroup = subsequences per tile, a multiple of 64 up to 1024.  One
+ *   workgroup per image.  coef must be ZERO where the images lie (the caller's memset on the same stream): only nonzero coefficients
+ *   are stored, the DC as the DIFFERENCE the file codes.  status[n] int32 is written for every image: 0, EP24JPEG_E_DATA (-4: an invalid
+ *   code, a run past coefficient 63, bits consumed behind the end of a restart segment, or fewer complete blocks than a segment must
+ *   hold; surplus bits and blocks at the end of a segment are ignored) or EP24_E_ARG (a descriptor row that does not fit the buffers:
+ *   nothing of that image is read or written).
+ * ep24_jpeg_dc: the same image_desc; turns the DC differences into values - a prefix sum per component in scan order, in int32, from zero
+ *   at every restart segment - and sets status[i] = EP24JPEG_E_DATA where a value leaves int16.  Runs behind ep24_jpeg_huffman on the
+ *   same stream; ep24_jpeg_idct then reads coef.
+ * No image index sits in a grid dimension's limit (n <= 2^31 / 3).  A store that a descriptor would send outside the image's
+ * coefficients is dropped.  EP24_E_ARG: a negative count, a null pointer with work to do, a misaligned buffer (descriptors 8 bytes,
+ * segment rows and status 4), another subseq_bytes or tile; n = 0 launches nothing. */
+int ep24_jpeg_huffman(const uint8_t* bytes, int64_t nbytes, const int64_t* image_desc, int n, const int32_t* segments, int64_t nseg,
+                      const uint8_t* table_specs, int subseq_bytes, int tile, void* coef, int64_t ncoef, int32_t* status, void* stream);
+int ep24_jpeg_dc(const int64_t* image_desc, int n, void* coef, int64_t ncoef, int32_t* status, void* stream);
+
 /* Baseline JPEG encode, the arithmetic half ("JPEG encode"): what libjpeg's default compress path computes in front of its
  * Huffman stage - 16-bit fixed-point RGB -> YCbCr, h2v1 / h2v2 chroma downsampling with its edge rules, the islow integer forward
  * DCT, quantisation, the dummy blocks of the MCU padding - in every coefficient, for a batch of images of any sizes and samplings in two

@@ -51,6 +51,41 @@ int ep24jpeg_parse(const uint8_t* bytes, int64_t n, ep24jpeg_header* header_out)
  * capacity (in int16) below ncoef is EP24JPEG_E_ARG.  On an error the contents of coef_out are unspecified (but in bounds). */
 int ep24jpeg_entropy_decode(const uint8_t* bytes, int64_t n, int16_t* coef_out, int64_t capacity);
 
+/* ---- the host side of the DEVICE entropy decoder (ep24_jpeg_huffman / ep24_jpeg_dc of libep24.so; DESIGN.md, "JPEG decode: Huffman
+ * stage on the GPU"): the marker walk without any Huffman work, and the kernel's phases run on the host ---- */
+
+#define EP24JPEG_MAX_SCAN (1 << 28)  /* the device decoder addresses the bits of a scan in 32 bits */
+
+typedef struct ep24jpeg_huff_spec {
+    uint8_t counts[16];              /* codes of length 1 .. 16 */
+    uint8_t symbols[256];
+    int32_t nsymbols;
+} ep24jpeg_huff_spec;
+
+typedef struct ep24jpeg_scan_info {
+    ep24jpeg_header header;
+    int32_t mcus_x, mcus_y;
+    int32_t blocks_per_mcu;
+    int32_t nseg;                    /* restart segments the scan must hold: ceil(MCUs / restart_interval), 1 without restarts */
+    int64_t scan_pos, scan_len;      /* the entropy-coded data: bytes[scan_pos, scan_pos + scan_len), up to the end of the last segment */
+    ep24jpeg_huff_spec dc[3], ac[3]; /* the tables of each component as the file specifies them */
+} ep24jpeg_scan_info;
+
+/* ep24jpeg_parse plus what the device needs to decode the one scan.  segments (may be null: only info is filled) receives nseg rows of
+ * {byte offset relative to scan_pos, length in bytes, MCUs the segment must hold}; seg_capacity (in rows) below nseg is EP24JPEG_E_ARG.
+ * A segment ends in front of the first FF that is not followed by 00; between two segments the walk accepts fill bytes and wants RSTn
+ * in sequence (EP24JPEG_E_DATA otherwise, as ep24jpeg_entropy_decode: "RSTn expected"), so a file with fewer segments than nseg is
+ * refused here.  Like ep24jpeg_entropy_decode it does not look behind the last segment: a file whose EOI is missing is accepted. */
+int ep24jpeg_scan_layout(const uint8_t* bytes, int64_t n, ep24jpeg_scan_info* info, int64_t* segments, int64_t seg_capacity);
+
+/* The device decoder with threads as loops (csrc/jpeg_huff_core.h is the text both run): subsequences of subseq_bytes (16, 32, 64, 128
+ * or 256) in tiles of `tile` (1 .. 1024) threads, speculative round 0, rounds until no end state changes, write pass, DC pass.  Output
+ * and codes as ep24jpeg_entropy_decode, with one difference in what is accepted: bytes left over at the end of a restart segment,
+ * behind the blocks it must hold, are ignored here, where ep24jpeg_entropy_decode wants the marker within its next refill ("RSTn
+ * expected") - 47 of 2 000 single-byte corruptions of a file with restart markers (csrc/jpeg_device_check.cpp --corrupt-rst).  *rounds_out (may be null): the largest number of rounds in which any thread of a tile decoded (round 0 included). */
+int ep24jpeg_selfsync_emulate(const uint8_t* bytes, int64_t n, int subseq_bytes, int tile, int16_t* coef_out, int64_t capacity,
+                              int32_t* rounds_out);
+
 /* ---- the writer: the host half of the baseline encoder (the arithmetic is ep24_jpeg_sample / ep24_jpeg_fdct of libep24.so) ---- */
 
 /* jpeg_set_quality's scaling of the Annex K tables, natural order: qt[0] luminance, qt[1] chrominance.  quality 1 .. 100
