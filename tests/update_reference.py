@@ -25,10 +25,11 @@ SENT16 = 0xFFA5
 SENT8 = 0xA5
 NAN32 = 0x7FC00000
 INT32_MIN = -2 ** 31
-_NP = {"f32": np.uint32, "bf16": np.uint16, "u8": np.uint8, "i32": np.int32, "i64": np.int64}
-_SENT = {"f32": SENT32, "bf16": SENT16, "u8": SENT8, "i32": 0x5A5A5A5A, "i64": 0x5A5A5A5A5A5A}
+SENT64 = 0xFFF5A5A5A5A5A5A5       # the float64 twin of SENT32: a negative NaN with a payload
+_NP = {"f32": np.uint32, "bf16": np.uint16, "u8": np.uint8, "i32": np.int32, "i64": np.int64, "f64": np.uint64}
+_SENT = {"f32": SENT32, "bf16": SENT16, "u8": SENT8, "i32": 0x5A5A5A5A, "i64": 0x5A5A5A5A5A5A, "f64": SENT64}
 _TORCH = {"f32": (np.int32, torch.float32), "bf16": (np.int16, torch.bfloat16), "u8": (np.uint8, torch.uint8),
-          "i32": (np.int32, torch.int32), "i64": (np.int64, torch.int64)}
+          "i32": (np.int32, torch.int32), "i64": (np.int64, torch.int64), "f64": (np.int64, torch.float64)}
 
 
 def r8(v):
