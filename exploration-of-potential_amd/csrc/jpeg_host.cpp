@@ -14,6 +14,7 @@
 
 #include "../../include/ep24_jpeg.h"
 #include "jpeg_huff_core.h"
+#include "jpeg_huffenc_core.h"
 
 namespace {
 
@@ -26,10 +27,6 @@ int fail(int code, const char* fmt, ...) {
     va_end(ap);
     return code;
 }
-
-const uint8_t kZigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                             41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                             30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
 
 enum { LOOK = 9 };
 
@@ -106,7 +103,7 @@ int parse(const uint8_t* d, int64_t n, Parsed& P) {
                 const int pq = s[q] >> 4, t = s[q] & 15;
                 const int need = pq ? 129 : 65;
                 if (pq > 1 || t > 3 || q + need > sl) return fail(EP24JPEG_E_DATA, "jpeg: bad quantisation table segment");
-                for (int k = 0; k < 64; ++k) qt[t][kZigzag[k]] = (uint16_t)(pq ? u16(s, q + 1 + 2 * k) : s[q + 1 + k]);
+                for (int k = 0; k < 64; ++k) qt[t][ep24huff_zigzag(k)] = (uint16_t)(pq ? u16(s, q + 1 + 2 * k) : s[q + 1 + k]);
                 qt_def[t] = true;
                 q += need;
             }
@@ -286,46 +283,6 @@ const uint8_t kBaseQ[2][64] = {
     {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99,
      99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99}};
 
-// the typical Huffman tables of Annex K.3: code counts per length 1 .. 16, then the symbols; [0] luminance, [1] chrominance
-const uint8_t kDcBits[2][16] = {{0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0}, {0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0}};
-const uint8_t kDcVals[12] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11};
-const uint8_t kAcBits[2][16] = {{0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 125}, {0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 119}};
-const uint8_t kAcVals[2][162] = {
-    {0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61, 0x07, 0x22, 0x71, 0x14, 0x32, 0x81, 0x91, 0xa1,
-     0x08, 0x23, 0x42, 0xb1, 0xc1, 0x15, 0x52, 0xd1, 0xf0, 0x24, 0x33, 0x62, 0x72, 0x82, 0x09, 0x0a, 0x16, 0x17, 0x18, 0x19, 0x1a, 0x25, 0x26,
-     0x27, 0x28, 0x29, 0x2a, 0x34, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56,
-     0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x83, 0x84, 0x85,
-     0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa,
-     0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6,
-     0xd7, 0xd8, 0xd9, 0xda, 0xe1, 0xe2, 0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf1, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9,
-     0xfa},
-    {0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07, 0x61, 0x71, 0x13, 0x22, 0x32, 0x81, 0x08, 0x14, 0x42,
-     0x91, 0xa1, 0xb1, 0xc1, 0x09, 0x23, 0x33, 0x52, 0xf0, 0x15, 0x62, 0x72, 0xd1, 0x0a, 0x16, 0x24, 0x34, 0xe1, 0x25, 0xf1, 0x17, 0x18, 0x19,
-     0x1a, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49, 0x4a, 0x53, 0x54, 0x55,
-     0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x82, 0x83,
-     0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8,
-     0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4,
-     0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe2, 0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9,
-     0xfa}};
-
-struct EncHuff {
-    uint16_t code[256];
-    uint8_t len[256];
-};
-
-void build_enc(EncHuff& e, const uint8_t* bits, const uint8_t* vals) {
-    memset(&e, 0, sizeof(e));
-    unsigned code = 0;
-    int k = 0;
-    for (int l = 1; l <= 16; ++l) {
-        for (int i = 0; i < bits[l - 1]; ++i, ++k) {
-            e.code[vals[k]] = (uint16_t)code++;
-            e.len[vals[k]] = (uint8_t)l;
-        }
-        code <<= 1;
-    }
-}
-
 // what ep24.jpeg._check refuses, and what the marker segments cannot say
 int check_header(const ep24jpeg_header& h, int& mcus_x, int& mcus_y) {
     mcus_x = mcus_y = 0;
@@ -398,14 +355,63 @@ inline void flush_bits(Writer& w) {                              // the last byt
 
 inline int bit_size(int a) { return a ? 32 - __builtin_clz((unsigned)a) : 0; }
 
-void put_dht(Writer& w, int tc_th, const uint8_t* bits, const uint8_t* vals) {
+// the Annex K table (ac: 0 / 1, t: 0 luminance, 1 chrominance) of csrc/jpeg_huffenc_core.h as a DHT segment
+void put_dht(Writer& w, int ac, int t) {
     int cnt = 0;
-    for (int i = 0; i < 16; ++i) cnt += bits[i];
+    for (int i = 0; i < 16; ++i) cnt += ac ? ep24huffenc_ac_bits(t, i) : ep24huffenc_dc_bits(t, i);
     put_u16(w, 0xFFC4);
     put_u16(w, 2 + 1 + 16 + cnt);
-    put_byte(w, (unsigned)tc_th);
-    for (int i = 0; i < 16; ++i) put_byte(w, bits[i]);
-    for (int i = 0; i < cnt; ++i) put_byte(w, vals[i]);
+    put_byte(w, (unsigned)((ac << 4) | t));
+    for (int i = 0; i < 16; ++i) put_byte(w, (unsigned)(ac ? ep24huffenc_ac_bits(t, i) : ep24huffenc_dc_bits(t, i)));
+    for (int i = 0; i < cnt; ++i) put_byte(w, (unsigned)(ac ? ep24huffenc_ac_val(t, i) : ep24huffenc_dc_val(t, i)));
+}
+
+// SOI up to and including the SOS header
+void put_header(Writer& w, const ep24jpeg_header& h) {
+    put_u16(w, 0xFFD8);
+    static const uint8_t kApp0[16] = {0x00, 0x10, 'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0};
+    put_u16(w, 0xFFE0);
+    for (int i = 0; i < 16; ++i) put_byte(w, kApp0[i]);
+    // Cb and Cr share table 1 when their tables are equal (what every common encoder writes); a third table otherwise
+    int tq[3] = {0, 1, 1}, ntab = h.ncomp == 1 ? 1 : 2;
+    if (h.ncomp == 3 && memcmp(h.qt[1], h.qt[2], sizeof(h.qt[1])) != 0) tq[2] = 2, ntab = 3;
+    for (int t = 0; t < ntab; ++t) {
+        put_u16(w, 0xFFDB);
+        put_u16(w, 67);
+        put_byte(w, (unsigned)t);
+        for (int k = 0; k < 64; ++k) put_byte(w, h.qt[t][ep24huff_zigzag(k)]);
+    }
+    put_u16(w, 0xFFC0);
+    put_u16(w, 8 + 3 * h.ncomp);
+    put_byte(w, 8);
+    put_u16(w, (unsigned)h.height);
+    put_u16(w, (unsigned)h.width);
+    put_byte(w, (unsigned)h.ncomp);
+    for (int c = 0; c < h.ncomp; ++c) {
+        put_byte(w, (unsigned)(c + 1));
+        put_byte(w, (unsigned)((h.h[c] << 4) | h.v[c]));
+        put_byte(w, (unsigned)tq[c]);
+    }
+    const int nh = h.ncomp == 1 ? 1 : 2;
+    for (int t = 0; t < nh; ++t) {
+        put_dht(w, 0, t);
+        put_dht(w, 1, t);
+    }
+    if (h.restart_interval > 0) {
+        put_u16(w, 0xFFDD);
+        put_u16(w, 4);
+        put_u16(w, (unsigned)h.restart_interval);
+    }
+    put_u16(w, 0xFFDA);
+    put_u16(w, 6 + 2 * h.ncomp);
+    put_byte(w, (unsigned)h.ncomp);
+    for (int c = 0; c < h.ncomp; ++c) {
+        put_byte(w, (unsigned)(c + 1));
+        put_byte(w, c ? 0x11u : 0x00u);
+    }
+    put_byte(w, 0);
+    put_byte(w, 63);
+    put_byte(w, 0);
 }
 
 }  // namespace
@@ -442,56 +448,10 @@ extern "C" int ep24jpeg_entropy_encode(const ep24jpeg_header* header, const int1
     if (capacity < bound) return fail(EP24JPEG_E_ARG, "ep24jpeg_entropy_encode: capacity %lld below the bound %lld", (long long)capacity, (long long)bound);
 
     Writer w = {out, 0, capacity, 0, 0};
-    put_u16(w, 0xFFD8);
-    static const uint8_t kApp0[16] = {0x00, 0x10, 'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0};
-    put_u16(w, 0xFFE0);
-    for (int i = 0; i < 16; ++i) put_byte(w, kApp0[i]);
-    // Cb and Cr share table 1 when their tables are equal (what every common encoder writes); a third table otherwise
-    int tq[3] = {0, 1, 1}, ntab = h.ncomp == 1 ? 1 : 2;
-    if (h.ncomp == 3 && memcmp(h.qt[1], h.qt[2], sizeof(h.qt[1])) != 0) tq[2] = 2, ntab = 3;
-    for (int t = 0; t < ntab; ++t) {
-        put_u16(w, 0xFFDB);
-        put_u16(w, 67);
-        put_byte(w, (unsigned)t);
-        for (int k = 0; k < 64; ++k) put_byte(w, h.qt[t][kZigzag[k]]);
-    }
-    put_u16(w, 0xFFC0);
-    put_u16(w, 8 + 3 * h.ncomp);
-    put_byte(w, 8);
-    put_u16(w, (unsigned)h.height);
-    put_u16(w, (unsigned)h.width);
-    put_byte(w, (unsigned)h.ncomp);
-    for (int c = 0; c < h.ncomp; ++c) {
-        put_byte(w, (unsigned)(c + 1));
-        put_byte(w, (unsigned)((h.h[c] << 4) | h.v[c]));
-        put_byte(w, (unsigned)tq[c]);
-    }
-    const int nh = h.ncomp == 1 ? 1 : 2;
-    for (int t = 0; t < nh; ++t) {
-        put_dht(w, 0x00 | t, kDcBits[t], kDcVals);
-        put_dht(w, 0x10 | t, kAcBits[t], kAcVals[t]);
-    }
-    if (h.restart_interval > 0) {
-        put_u16(w, 0xFFDD);
-        put_u16(w, 4);
-        put_u16(w, (unsigned)h.restart_interval);
-    }
-    put_u16(w, 0xFFDA);
-    put_u16(w, 6 + 2 * h.ncomp);
-    put_byte(w, (unsigned)h.ncomp);
-    for (int c = 0; c < h.ncomp; ++c) {
-        put_byte(w, (unsigned)(c + 1));
-        put_byte(w, c ? 0x11u : 0x00u);
-    }
-    put_byte(w, 0);
-    put_byte(w, 63);
-    put_byte(w, 0);
+    put_header(w, h);
 
-    EncHuff dc[2], ac[2];
-    for (int t = 0; t < 2; ++t) {
-        build_enc(dc[t], kDcBits[t], kDcVals);
-        build_enc(ac[t], kAcBits[t], kAcVals[t]);
-    }
+    uint32_t tab[EP24HUFFENC_TABLE] = {0};                 // code | length << 16 per symbol, the tables the device encoder builds
+    for (int i = 0; i < EP24HUFFENC_ENTRIES; ++i) ep24huffenc_fill(tab, i);
     const int16_t* base[3];
     int64_t off = 0;
     for (int c = 0; c < h.ncomp; ++c) {
@@ -514,8 +474,8 @@ extern "C" int ep24jpeg_entropy_encode(const ep24jpeg_header* header, const int1
                 --left;
             }
             for (int c = 0; c < h.ncomp; ++c) {
-                const EncHuff& hdc = dc[c ? 1 : 0];
-                const EncHuff& hac = ac[c ? 1 : 0];
+                const uint32_t* hdc = tab + EP24HUFFENC_DC(c ? 1 : 0);
+                const uint32_t* hac = tab + EP24HUFFENC_AC(c ? 1 : 0);
                 for (int by = 0; by < h.v[c]; ++by)
                     for (int bx = 0; bx < h.h[c]; ++bx) {
                         const int16_t* blk = base[c] + ((int64_t)(my * h.v[c] + by) * h.blocks_w[c] + (mx * h.h[c] + bx)) * 64;
@@ -525,11 +485,11 @@ extern "C" int ep24jpeg_entropy_encode(const ep24jpeg_header* header, const int1
                             return fail(EP24JPEG_E_ARG, "jpeg encode: DC difference %d in MCU %d is outside baseline's +-2047", diff, my * mcus_x + mx);
                         int a = diff < 0 ? -diff : diff;
                         int s = bit_size(a);
-                        put_bits(w, hdc.code[s], hdc.len[s]);
+                        put_bits(w, hdc[s] & 0xFFFFu, (int)(hdc[s] >> 16));
                         if (s) put_bits(w, (unsigned)(diff < 0 ? diff - 1 : diff) & ((1u << s) - 1), s);
                         int run = 0;
                         for (int k = 1; k < 64; ++k) {
-                            const int v = blk[kZigzag[k]];
+                            const int v = blk[ep24huff_zigzag(k)];
                             if (v == 0) {
                                 ++run;
                                 continue;
@@ -537,23 +497,140 @@ extern "C" int ep24jpeg_entropy_encode(const ep24jpeg_header* header, const int1
                             if (v < -1023 || v > 1023)
                                 return fail(EP24JPEG_E_ARG, "jpeg encode: AC coefficient %d in MCU %d is outside baseline's +-1023", v, my * mcus_x + mx);
                             while (run > 15) {
-                                put_bits(w, hac.code[0xF0], hac.len[0xF0]);
+                                put_bits(w, hac[0xF0] & 0xFFFFu, (int)(hac[0xF0] >> 16));
                                 run -= 16;
                             }
                             a = v < 0 ? -v : v;
                             s = bit_size(a);
                             const int sym = (run << 4) | s;
-                            put_bits(w, hac.code[sym], hac.len[sym]);
+                            put_bits(w, hac[sym] & 0xFFFFu, (int)(hac[sym] >> 16));
                             put_bits(w, (unsigned)(v < 0 ? v - 1 : v) & ((1u << s) - 1), s);
                             run = 0;
                         }
-                        if (run) put_bits(w, hac.code[0], hac.len[0]);
+                        if (run) put_bits(w, hac[0] & 0xFFFFu, (int)(hac[0] >> 16));
                     }
             }
         }
     flush_bits(w);
     put_u16(w, 0xFFD9);
     if (w.p > capacity) return fail(EP24JPEG_E_ARG, "ep24jpeg_entropy_encode: the stream outgrew its bound (%lld > %lld)", (long long)w.p, (long long)capacity);
+    *nbytes = w.p;
+    return EP24JPEG_OK;
+}
+
+extern "C" int ep24jpeg_encode_header(const ep24jpeg_header* header, uint8_t* out, int64_t capacity, int64_t* nbytes) {
+    if (!header || !out || !nbytes) return fail(EP24JPEG_E_ARG, "ep24jpeg_encode_header: null pointer");
+    int mcus_x, mcus_y;
+    const int rc = check_header(*header, mcus_x, mcus_y);
+    if (rc) return rc;
+    Writer w = {out, 0, capacity < 0 ? 0 : capacity, 0, 0};
+    put_header(w, *header);
+    if (w.p > capacity) return fail(EP24JPEG_E_ARG, "ep24jpeg_encode_header: capacity %lld below the %lld bytes of the header", (long long)capacity, (long long)w.p);
+    *nbytes = w.p;
+    return EP24JPEG_OK;
+}
+
+// ---- the device encoder's phases with threads as loops (csrc/jpeg_huffenc_core.h is the text both run) ----
+
+namespace {
+
+// the emit pass's store on the host: every word is ORed into the zeroed buffer, and a word a block claims to own must have been zero
+struct EmuStore {
+    uint32_t* words;
+    int64_t cap;
+    int bad;
+    void operator()(int64_t w, uint32_t v, bool owned) {
+        if (w < 0 || w >= cap || (owned && words[w])) {
+            bad = 1;
+            return;
+        }
+        words[w] |= v;
+    }
+};
+
+}  // namespace
+
+extern "C" int ep24jpeg_encode_emulate(const ep24jpeg_header* header, const int16_t* coef, int64_t ncoef, int tile, uint8_t* out,
+                                       int64_t capacity, int64_t* nbytes) {
+    if (!header || !coef || !out || !nbytes) return fail(EP24JPEG_E_ARG, "ep24jpeg_encode_emulate: null pointer");
+    const ep24jpeg_header& h = *header;
+    int mcus_x, mcus_y;
+    int rc = check_header(h, mcus_x, mcus_y);
+    if (rc) return rc;
+    if (ncoef != h.ncoef) return fail(EP24JPEG_E_ARG, "ep24jpeg_encode_emulate: %lld coefficients given, the header holds %lld", (long long)ncoef, (long long)h.ncoef);
+    if (tile < 1 || tile > 1 << 20) return fail(EP24JPEG_E_ARG, "ep24jpeg_encode_emulate: a tile of %d blocks (1 .. 2^20)", tile);
+    const int64_t bound = encode_bound(h, mcus_x, mcus_y);
+    if (capacity < bound) return fail(EP24JPEG_E_ARG, "ep24jpeg_encode_emulate: capacity %lld below the bound %lld", (long long)capacity, (long long)bound);
+
+    // the descriptor rows ep24.jpeg uploads for one image, and what the kernels make of them
+    const int64_t mcus = (int64_t)mcus_x * mcus_y, ri = h.restart_interval;
+    const int bpm = h.ncomp == 1 ? 1 : h.h[0] * h.v[0] + 2;
+    const int64_t nblocks = mcus * bpm, nseg = ri ? (mcus + ri - 1) / ri : 1;
+    int64_t rows[2 * EP24HUFFENC_DESC] = {0};
+    rows[2] = h.ncomp, rows[3] = h.h[0], rows[4] = h.v[0], rows[5] = mcus_x, rows[6] = mcus_y, rows[7] = ri;
+    for (int c = 1; c < h.ncomp; ++c) rows[8 + c] = rows[8 + c - 1] + h.nblocks[c - 1];
+    rows[EP24HUFFENC_DESC] = nblocks, rows[EP24HUFFENC_DESC + 1] = nseg;
+    ep24huffenc_image I;
+    if (!ep24huffenc_load(rows, nblocks, nseg, ncoef, I)) return fail(EP24JPEG_E_ARG, "ep24jpeg_encode_emulate: the descriptor does not fit the header");
+    uint32_t tab[EP24HUFFENC_TABLE] = {0};
+    for (int i = 0; i < EP24HUFFENC_ENTRIES; ++i) ep24huffenc_fill(tab, i);
+
+    // count: every block on its own
+    std::vector<int64_t> pos((size_t)nblocks);
+    int status = 0;
+    for (int64_t q = 0; q < nblocks; ++q) {
+        const ep24huffenc_where W = ep24huffenc_locate(I, q);
+        ep24huffenc_counter cnt = {0};
+        status |= ep24huffenc_block(coef + W.at, W.pred_at < 0 ? 0 : coef[W.pred_at], tab + EP24HUFFENC_DC(W.chroma), tab + EP24HUFFENC_AC(W.chroma), cnt);
+        pos[(size_t)q] = cnt.bits;
+    }
+    if (status & EP24HUFFENC_BAD_DC) return fail(EP24JPEG_E_ARG, "jpeg encode: a DC difference is outside baseline's +-2047");
+    if (status & EP24HUFFENC_BAD_AC) return fail(EP24JPEG_E_ARG, "jpeg encode: an AC coefficient is outside baseline's +-1023");
+    // scan: inclusive sums over the image, then the segments' bits and first words
+    for (int64_t q = 1; q < nblocks; ++q) pos[(size_t)q] += pos[(size_t)q - 1];
+    std::vector<int64_t> seg((size_t)nseg * 2);
+    int64_t nwords = 0;
+    for (int64_t s = 0; s < nseg; ++s) {
+        const int64_t b = s * ri * bpm, e = ri && (s + 1) * ri * bpm < nblocks ? (s + 1) * ri * bpm : nblocks;
+        const int64_t bits = pos[(size_t)e - 1] - (b ? pos[(size_t)b - 1] : 0);
+        seg[(size_t)(2 * s)] = nwords, seg[(size_t)(2 * s + 1)] = bits;
+        nwords += (bits + 31) >> 5;
+    }
+    // emit: the last tile first, and the last block of a tile first
+    std::vector<uint32_t> words((size_t)nwords, 0u);
+    EmuStore st = {words.data(), nwords, 0};
+    for (int64_t t0 = (nblocks - 1) / tile * tile; t0 >= 0; t0 -= tile)
+        for (int64_t q = (t0 + tile < nblocks ? t0 + tile : nblocks) - 1; q >= t0; --q) {
+            const ep24huffenc_where W = ep24huffenc_locate(I, q);
+            const int64_t in_seg = (q ? pos[(size_t)q - 1] : 0) - (W.seg_block ? pos[(size_t)W.seg_block - 1] : 0);
+            ep24huffenc_emitter<EmuStore> em;
+            em.begin(32 * seg[(size_t)(2 * W.seg)] + in_seg, &st);
+            ep24huffenc_block(coef + W.at, W.pred_at < 0 ? 0 : coef[W.pred_at], tab + EP24HUFFENC_DC(W.chroma), tab + EP24HUFFENC_AC(W.chroma), em);
+            if (W.seg_last) em.pad();
+            em.finish();
+        }
+    if (st.bad) return fail(EP24JPEG_E_ARG, "ep24jpeg_encode_emulate: the emit pass left its words (count and emit disagree)");
+    // stuff: count per chunk, sum, scatter - the last chunk first
+    const int64_t nchunks = (nwords + EP24HUFFENC_CHUNK_WORDS - 1) / EP24HUFFENC_CHUNK_WORDS;
+    std::vector<int64_t> at((size_t)nchunks + 1, 0);
+    for (int64_t c = 0; c < nchunks; ++c) {
+        ep24huffenc_byte_counter bc = {0};
+        const int64_t w1 = (c + 1) * EP24HUFFENC_CHUNK_WORDS;
+        ep24huffenc_chunk(words.data(), seg.data(), nseg, c * EP24HUFFENC_CHUNK_WORDS, w1 < nwords ? w1 : nwords, bc);
+        at[(size_t)c + 1] = at[(size_t)c] + bc.n;
+    }
+    Writer w = {out, 0, capacity, 0, 0};
+    put_header(w, h);
+    const int64_t scan_bytes = at[(size_t)nchunks];
+    if (w.p + scan_bytes + 2 > capacity) return fail(EP24JPEG_E_ARG, "ep24jpeg_encode_emulate: the stream outgrew its bound");
+    for (int64_t c = nchunks - 1; c >= 0; --c) {
+        ep24huffenc_byte_writer bw = {out + w.p, at[(size_t)c], scan_bytes, 0};
+        const int64_t w1 = (c + 1) * EP24HUFFENC_CHUNK_WORDS;
+        ep24huffenc_chunk(words.data(), seg.data(), nseg, c * EP24HUFFENC_CHUNK_WORDS, w1 < nwords ? w1 : nwords, bw);
+        if (bw.dropped || bw.p != at[(size_t)c + 1]) return fail(EP24JPEG_E_ARG, "ep24jpeg_encode_emulate: the stuff passes disagree");
+    }
+    w.p += scan_bytes;
+    put_u16(w, 0xFFD9);
     *nbytes = w.p;
     return EP24JPEG_OK;
 }
@@ -630,7 +707,7 @@ extern "C" int ep24jpeg_entropy_decode(const uint8_t* bytes, int64_t n, int16_t*
                             }
                             k += r;
                             if (k > 63) return fail(EP24JPEG_E_DATA, "jpeg: AC run past the end of a block in MCU %d", my * P.mcus_x + mx);
-                            blk[kZigzag[k]] = (int16_t)receive_extend(b, s);
+                            blk[ep24huff_zigzag(k)] = (int16_t)receive_extend(b, s);
                             ++k;
                         }
                         if (b.pad > b.n) return fail(EP24JPEG_E_DATA, "jpeg: the entropy-coded data ends in MCU %d of %d", my * P.mcus_x + mx, P.mcus_x * P.mcus_y);

@@ -21,6 +21,13 @@ The writer mirrors the reader:
     data = entropy_encode(coefs[i])        # host: libep24jpeg.so (markers, Annex K Huffman tables, the scan), no GPU
     datas = encode([image, ...])           # both
 
+The writer's Huffman stage can run on the GPU as well ("JPEG encode: Huffman stage on the GPU"); the coefficients then
+never leave the device and only the finished scans cross the bus:
+
+    datas = encode([image, ...], entropy="device")        # sample, FDCT, ep24_jpeg_huffenc_count + _emit; header and FF D9 on the host
+    datas = entropy_encode_device([coefs, ...])           # the kernels on uploaded coefficients (tests and tools)
+    data = encode_emulate(coefs)           # host: the kernels' phases with threads as loops (libep24jpeg.so), no GPU
+
 The files are what libjpeg-turbo's default compress path (Pillow, ``cv2.imwrite``) writes from the same pixels at the same quality
 and sampling, byte for byte: baseline, 4:4:4 / 4:2:2 / 4:2:0 or one component, quality 1 .. 100 or explicit tables, optional restart
 markers.  Input that is not uint8, not on the GPU or above 8192 a side raises ``JpegError``.  Optimised Huffman tables, progressive
@@ -188,6 +195,11 @@ def host_lib():
         L.ep24jpeg_selfsync_emulate.restype = ctypes.c_int
         L.ep24jpeg_selfsync_emulate.argtypes = [ctypes.c_char_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64,
                                                 ctypes.POINTER(ctypes.c_int32)]
+        L.ep24jpeg_encode_header.restype = ctypes.c_int
+        L.ep24jpeg_encode_header.argtypes = [ctypes.POINTER(_Header), ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]
+        L.ep24jpeg_encode_emulate.restype = ctypes.c_int
+        L.ep24jpeg_encode_emulate.argtypes = [ctypes.POINTER(_Header), ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p,
+                                              ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]
         if L.ep24jpeg_abi_version() != ABI_VERSION:
             raise Ep24Error("ep24: %s reports ABI version %d, ep24.jpeg expects %d - rebuild the library" %
                             (HOST_LIB_PATH, L.ep24jpeg_abi_version(), ABI_VERSION))
@@ -622,9 +634,7 @@ def _c_header(hd):
     return c
 
 
-def entropy_encode(coefficients):
-    """JpegCoefficients -> the bytes of a baseline JFIF file: the host half of the writer (markers, the Annex K Huffman tables, the
-    interleaved scan with restart markers every ``header.restart_interval`` MCUs).  Uses the host library only."""
+def _host_encode(coefficients, tile=None):
     L, hd = host_lib(), coefficients.header
     coef = coefficients.coef
     if not isinstance(coef, np.ndarray) or coef.dtype != np.int16 or coef.ndim != 1:
@@ -636,10 +646,138 @@ def entropy_encode(coefficients):
         _raise(L, bound)
     out = np.empty(bound, dtype=np.uint8)                  # untouched pages of it cost nothing
     n = ctypes.c_int64(0)
-    rc = L.ep24jpeg_entropy_encode(ctypes.byref(c), coef.ctypes.data, coef.size, out.ctypes.data, out.size, ctypes.byref(n))
+    if tile is None:
+        rc = L.ep24jpeg_entropy_encode(ctypes.byref(c), coef.ctypes.data, coef.size, out.ctypes.data, out.size, ctypes.byref(n))
+    else:
+        rc = L.ep24jpeg_encode_emulate(ctypes.byref(c), coef.ctypes.data, coef.size, int(tile), out.ctypes.data, out.size, ctypes.byref(n))
     if rc:
         _raise(L, rc)
     return out[:n.value].tobytes()
+
+
+def entropy_encode(coefficients):
+    """JpegCoefficients -> the bytes of a baseline JFIF file: the host half of the writer (markers, the Annex K Huffman tables, the
+    interleaved scan with restart markers every ``header.restart_interval`` MCUs).  Uses the host library only."""
+    return _host_encode(coefficients)
+
+
+EMIT_TILE = 256                                           # blocks per workgroup of the device encoder's count and emit kernels
+STUFF_CHUNK, STUFF_TILE = 64, 1024                        # unstuffed bytes per item of its stuff passes, items per workgroup round
+STATUS_BAD_DC, STATUS_BAD_AC, STATUS_BAD_STORE = 1, 2, 4  # bits of the device encoder's status words (csrc/jpeg_huffenc_core.h)
+stats = {"d2h_bytes": 0}                                  # bytes the writer copied from the device so far (tools/jpeg_encode_device_timing.py)
+
+
+def encode_emulate(coefficients, tile=EMIT_TILE):
+    """``entropy_encode`` by the device encoder's phases run on the host (``ep24jpeg_encode_emulate``): count, scan, emit by ORing into
+    zeroed words - tiles of ``tile`` blocks last first - and the stuff passes.  For tests and tools; uses the host library only."""
+    return _host_encode(coefficients, int(tile))
+
+
+def encode_header(header):
+    """-> the bytes in front of the entropy-coded data: SOI up to and including the SOS header.  Host library only."""
+    L, c = host_lib(), _c_header(header)
+    out = np.empty(1024, dtype=np.uint8)
+    n = ctypes.c_int64(0)
+    rc = L.ep24jpeg_encode_header(ctypes.byref(c), out.ctypes.data, out.size, ctypes.byref(n))
+    if rc:
+        _raise(L, rc)
+    return out[:n.value].tobytes()
+
+
+def _huffenc_desc(headers):
+    """image_desc[n + 1][16] of ep24_jpeg_huffenc_count / _emit for images whose planes lie back to back in header order."""
+    rows, blocks, segs = [], 0, 0
+    for hd in headers:
+        mx, my = hd.blocks_w[0] // hd.h[0], hd.blocks_h[0] // hd.v[0]
+        first, b = [], blocks
+        for c in range(3):
+            first.append(b if c < hd.ncomp else 0)
+            b += hd.nblocks[c] if c < hd.ncomp else 0
+        ri = hd.restart_interval
+        rows.append([blocks, segs, hd.ncomp, hd.h[0], hd.v[0], mx, my, ri] + first + [0] * 5)
+        blocks, segs = b, segs + (-(-mx * my // ri) if ri else 1)
+    rows.append([blocks, segs] + [0] * 14)
+    return np.asarray(rows, dtype=np.int64), blocks, segs
+
+
+def _entropy_device(headers, coef, dev):
+    """The device Huffman stage: coef (int16 device tensor: the planes of ``headers`` back to back) -> (the entropy-coded bytes of every
+    image, restart markers included, as a list of bytes; the status words as numpy int32).  Two small reads wait for the stream: the
+    word totals, from which the word and the output buffer are sized, then the offsets, the status words and the bytes themselves."""
+    import torch
+    from . import _lib
+    desc, blocks, segs = _huffenc_desc(headers)
+    n = len(headers)
+    if coef.numel() != 64 * blocks:
+        raise JpegError(EP24_E_ARG, "encode: the coefficient buffer does not hold the %d blocks of the headers" % blocks)
+    with torch.cuda.device(dev):
+        d = torch.from_numpy(desc.reshape(-1)).to(dev, non_blocking=True)
+        pos = torch.empty(blocks, dtype=torch.int64, device=dev)
+        seg = torch.empty(2 * segs, dtype=torch.int64, device=dev)
+        sums = torch.empty(4 * n + 2, dtype=torch.int64, device=dev)      # words per image, bytes per image, word_base[n + 1], offsets[n + 1]
+        status = torch.zeros(n, dtype=torch.int32, device=dev)
+        s, p = _lib.stream_ptr(), sums.data_ptr()
+        p_words, p_bytes, p_base, p_off = p, p + 8 * n, p + 16 * n, p + 8 * (3 * n + 1)
+        _lib.call("jpeg_huffenc_count", _lib.ptr(coef), coef.numel(), _lib.ptr(d), n, blocks, segs, _lib.ptr(pos), _lib.ptr(seg), p_words,
+                  p_base, _lib.ptr(status), s)
+        base = sums[2 * n:3 * n + 1].cpu().numpy()          # first read-back: the unstuffed words in front of every image
+        nwords = int(base[n])
+        words = torch.zeros(max(nwords, 1), dtype=torch.int32, device=dev)
+        cap = 8 * nwords + 2 * segs + 16                   # every byte stuffed, a marker per segment
+        out = torch.empty(cap, dtype=torch.uint8, device=dev)
+        _lib.call("jpeg_huffenc_emit", _lib.ptr(coef), coef.numel(), _lib.ptr(d), n, blocks, segs, _lib.ptr(pos), _lib.ptr(seg), p_base,
+                  _lib.ptr(words), nwords, p_bytes, p_off, _lib.ptr(out), cap, _lib.ptr(status), s)
+        off = sums[3 * n + 1:].cpu().numpy()                # second read-back: where every image's bytes lie
+        st = status.cpu().numpy()
+        total = int(off[n])
+        flat = out[:min(max(total, 0), cap)].cpu().numpy()
+    stats["d2h_bytes"] += base.nbytes + off.nbytes + st.nbytes + flat.nbytes
+    if total > cap or (np.diff(off) < 0).any():
+        raise JpegError(EP24_E_ARG, "encode: the device encoder's offsets do not fit its output buffer")
+    return [flat[int(off[i]):int(off[i + 1])].tobytes() for i in range(n)], st
+
+
+def _check_encode_status(st):
+    for i, code in enumerate(int(c) for c in st):
+        if code < 0:
+            raise JpegError(EP24_E_ARG, "item %d: the device encoder refused its descriptor (status %d)" % (i, code))
+        if code & STATUS_BAD_DC:
+            raise JpegError(EP24_E_ARG, "item %d: a DC difference is outside baseline's +-2047 (status %d)" % (i, code))
+        if code & STATUS_BAD_AC:
+            raise JpegError(EP24_E_ARG, "item %d: an AC coefficient is outside baseline's +-1023 (status %d)" % (i, code))
+        if code:
+            raise JpegError(EP24_E_ARG, "item %d: the device encoder dropped a store outside its buffers (status %d)" % (i, code))
+
+
+def _assemble(headers, scans):
+    return [encode_header(hd) + sc + b"\xff\xd9" for hd, sc in zip(headers, scans)]
+
+
+def entropy_encode_device(coefficients, device="cuda:0"):
+    """list of JpegCoefficients -> list of files as bytes, equal to ``entropy_encode`` of each: the coefficients are uploaded and coded
+    by ep24_jpeg_huffenc_count + ep24_jpeg_huffenc_emit; header and FF D9 are added on the host.  The status words are read once: a DC
+    difference outside +-2047 or an AC coefficient outside +-1023 raises JpegError(EP24_E_ARG) that names the item and the kind.  For
+    tests and tools: the product's coefficients are on the device already (``encode(entropy="device")``)."""
+    from . import _lib
+    _lib.require_gpu()
+    items = list(coefficients)
+    L = host_lib()
+    for i, it in enumerate(items):
+        coef = it.coef
+        if not isinstance(coef, np.ndarray) or coef.dtype != np.int16 or coef.ndim != 1 or coef.size != it.header.ncoef:
+            raise JpegError(EP24_E_ARG, "entropy_encode_device: item %d: the coefficients must be the header's %d int16 values" % (i, it.header.ncoef))
+        bound = L.ep24jpeg_encode_bound(ctypes.byref(_c_header(it.header)))
+        if bound < 0:
+            _raise(L, bound)
+    if not items:
+        return []
+    import torch
+    dev = torch.device(device)
+    coef = torch.from_numpy(np.concatenate([it.coef for it in items])).to(dev)
+    headers = [it.header for it in items]
+    scans, st = _entropy_device(headers, coef, dev)
+    _check_encode_status(st)
+    return _assemble(headers, scans)
 
 
 def forward(images, quality=95, subsampling="4:2:0", bgr=True, restart_interval=0):
@@ -648,6 +786,21 @@ def forward(images, quality=95, subsampling="4:2:0", bgr=True, restart_interval=
     whose coefficients equal libjpeg's at these tables.  ``quality``: 1 .. 100, or explicit tables (``_tables``).  One descriptor
     upload, ep24_jpeg_sample + ep24_jpeg_fdct on the current stream, one device-to-host copy.  The pixels are read where they lie:
     a view with a row stride (a crop of a wider tensor) is not copied first (only a tensor whose pixels are not packed is)."""
+    headers, coef, _ = _forward_device(images, quality, subsampling, bgr, restart_interval)
+    if not headers:
+        return []
+    flat = coef.cpu().numpy()                              # waits for the stream
+    stats["d2h_bytes"] += flat.nbytes
+    out, p = [], 0
+    for hd in headers:
+        out.append(JpegCoefficients(hd, flat[p:p + hd.ncoef]))
+        p += hd.ncoef
+    return out
+
+
+def _forward_device(images, quality, subsampling, bgr, restart_interval):
+    """``forward`` without its copy -> (headers, the int16 coefficients of all images on the device, the device); ([], None, None)
+    for no images."""
     from . import _lib
     images = list(images)
     qt = _tables(quality)
@@ -656,7 +809,7 @@ def forward(images, quality=95, subsampling="4:2:0", bgr=True, restart_interval=
     if not 0 <= int(restart_interval) <= 65535:
         raise JpegError(EP24_E_ARG, "encode: restart interval %r outside 0 .. 65535" % (restart_interval,))
     if not images:
-        return []
+        return [], None, None
     import torch
     srcs = []
     for i, im in enumerate(images):
@@ -701,18 +854,29 @@ def forward(images, quality=95, subsampling="4:2:0", bgr=True, restart_interval=
         base, s = buf.data_ptr(), _lib.stream_ptr()
         _lib.call("jpeg_sample", base + o_id, len(srcs), groups, _lib.ptr(planes), plane_off, s)
         _lib.call("jpeg_fdct", _lib.ptr(planes), plane_off, base, len(qt), base + o_pd, len(pdesc) - 1, blocks, _lib.ptr(coef), s)
-        flat = coef.cpu().numpy()                          # waits for the stream: srcs (and any packed copies) outlive the kernels
-    out, p = [], 0
-    for hd in headers:
-        out.append(JpegCoefficients(hd, flat[p:p + hd.ncoef]))
-        p += hd.ncoef
-    return out
+    # the caching allocator hands the blocks of srcs' packed copies, buf and planes out again to work of this stream only
+    return headers, coef, dev
 
 
-def encode(images, quality=95, subsampling="4:2:0", bgr=True, restart_interval=0):
-    """list of uint8 device images -> list of JPEG files as bytes: one ``forward``, then ``entropy_encode`` of each.  The default is
-    what ``cv2.imwrite`` writes: quality 95 at 4:2:0, BGR input."""
-    return [entropy_encode(c) for c in forward(images, quality, subsampling, bgr, restart_interval)]
+def encode(images, quality=95, subsampling="4:2:0", bgr=True, restart_interval=0, entropy="host"):
+    """list of uint8 device images -> list of JPEG files as bytes.  The default is what ``cv2.imwrite`` writes: quality 95 at 4:2:0, BGR
+    input.  ``entropy="host"``: one ``forward``, then ``entropy_encode`` of each.  ``entropy="device"``: the coefficients stay on the
+    device, ep24_jpeg_huffenc_count + ep24_jpeg_huffenc_emit code them there, and only the finished scans are copied; header and FF D9
+    are added on the host.  The same bytes either way."""
+    if entropy not in ("host", "device"):
+        raise JpegError(EP24_E_ARG, "encode: entropy must be 'host' or 'device', got %r" % (entropy,))
+    if entropy == "host":
+        return [entropy_encode(c) for c in forward(images, quality, subsampling, bgr, restart_interval)]
+    images = list(images)
+    if images:
+        from . import _lib
+        _lib.require_gpu()
+    headers, coef, dev = _forward_device(images, quality, subsampling, bgr, restart_interval)
+    if not headers:
+        return []
+    scans, st = _entropy_device(headers, coef, dev)
+    _check_encode_status(st)
+    return _assemble(headers, scans)
 
 
 def finish_checked(images, device="cuda:0", bgr=True):

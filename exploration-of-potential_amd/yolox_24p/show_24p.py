@@ -96,11 +96,12 @@ def resolve_jpeg_encoder(choice):
     return choice
 
 
-def write_images(paths, images, jpeg_encoder="auto", jpeg_quality=None):
+def write_images(paths, images, jpeg_encoder="auto", jpeg_quality=None, jpeg_entropy="host"):
     """Saves a batch: uint8 [h, w, 3] RGB numpy arrays or (device) tensors.  ``.jpg`` / ``.jpeg`` names go through ``ep24.jpeg.encode``
     with the native encoder - every one of the batch in one call, straight from the device tensors, at quality 95 and 4:2:0 (what
     ``cv2.imwrite`` writes) unless ``jpeg_quality`` says otherwise - and through PIL with the other (its own defaults unless
-    ``jpeg_quality`` is given)."""
+    ``jpeg_quality`` is given).  ``jpeg_entropy``: where the native encoder's Huffman stage runs, ``host`` or ``device`` (the same
+    files either way; with ``device`` only the finished scans leave the GPU)."""
     native = []
     for path, img in zip(paths, images):
         ext = os.path.splitext(path)[1].lower()
@@ -121,14 +122,15 @@ def write_images(paths, images, jpeg_encoder="auto", jpeg_quality=None):
     if native:
         from ep24 import jpeg
         tensors = [t if t.is_cuda else t.cuda() for _, t in native]
-        datas = jpeg.encode(tensors, quality=95 if jpeg_quality is None else int(jpeg_quality), subsampling="4:2:0", bgr=False)
+        datas = jpeg.encode(tensors, quality=95 if jpeg_quality is None else int(jpeg_quality), subsampling="4:2:0", bgr=False,
+                            entropy=jpeg_entropy)
         for (path, _), data in zip(native, datas):
             with open(path, "wb") as fh:
                 fh.write(data)
 
 
-def write_image(path, img, jpeg_encoder="auto", jpeg_quality=None):
-    write_images([path], [img], jpeg_encoder, jpeg_quality)
+def write_image(path, img, jpeg_encoder="auto", jpeg_quality=None, jpeg_entropy="host"):
+    write_images([path], [img], jpeg_encoder, jpeg_quality, jpeg_entropy)
 
 
 def list_images(load_path):
@@ -208,7 +210,8 @@ class Evaluator:
                     stem = os.path.splitext(name)[0]
                     segm.add(int(stem) if stem.isascii() and stem.isdigit() else stem, dets, ratio, (int(img.shape[0]), int(img.shape[1])))
                 print("%s: %d detections" % (name, rows.shape[0]))
-            write_images([os.path.join(self.save_folder, f) for f in names], drawn_batch, args.jpeg_encoder, args.jpeg_quality)
+            write_images([os.path.join(self.save_folder, f) for f in names], drawn_batch, args.jpeg_encoder, args.jpeg_quality,
+                         getattr(args, "jpeg_entropy", "host"))
         with open(os.path.join(self.save_folder, "detections.json"), "w") as fh:
             json.dump({"input_size": list(self.input_size), "conf": args.conf, "nms": args.nms, "nms_iou": args.nms_iou,
                        "draw_conf": args.draw_conf, "images": records}, fh, indent=1)
@@ -245,6 +248,8 @@ def make_parser():
                    "project's own baseline encoder (ep24.jpeg: arithmetic on the GPU); auto = PIL where it is installed, native otherwise")
     p.add_argument("--jpeg-quality", default=None, type=int, metavar="Q", help="quality 1..100 of .jpg results (native default: 95 at "
                    "4:2:0, what cv2.imwrite writes; PIL keeps its own default when the flag is absent)")
+    p.add_argument("--jpeg-entropy", default="host", choices=["host", "device"], help="the native encoder's Huffman stage: on the host "
+                   "(the int16 coefficients are copied back) or on the GPU (only the finished scans are); the same files either way")
     p.add_argument("--device", default="cuda", type=str, help="cuda or cuda:N (the ep24 path has no CPU fallback: cpu is refused)")
     return p
 

@@ -1004,6 +1004,37 @@ int ep24_jpeg_sample(const int64_t* image_desc, int n, int64_t total_groups, uin
 int ep24_jpeg_fdct(const uint8_t* planes, int64_t plane_bytes, const void* qt, int nqt, const int64_t* plane_desc, int n_planes,
                    int64_t total_blocks, void* coef, void* stream);
 
+/* Baseline JPEG encode, the Huffman stage on the device ("JPEG encode: Huffman stage on the GPU"): the coefficients
+ * ep24_jpeg_fdct leaves on the device -> the entropy-coded bytes of every image (FF 00 stuffing, 1-padding, RSTn markers; no header, no
+ * EOI), back to back in one buffer, byte for byte what ep24jpeg_entropy_encode of libep24jpeg.so writes between the SOS header and FF D9
+ * with the Annex K tables.  The block walk, the bit emitter and the stuffing are csrc/jpeg_huffenc_core.h, which ep24jpeg_encode_emulate
+ * runs on the host.  Shared inputs: coef (int16, ncoef values, ep24_jpeg_idct's layout); image_desc[n + 1][16] int64 = {0 first block of
+ * the image in SCAN order (MCU by MCU: the luma component's h x v blocks row by row, then Cb, then Cr; cumulative, image 0: 0), 1 first
+ * restart segment of the image (cumulative; an image has ceil(MCUs / interval) of them, 1 without restarts), 2 components (1 or 3), 3 / 4
+ * luma sampling h / v (1 x 1, 2 x 1 or 2 x 2; chroma is 1 x 1), 5 / 6 MCUs per row / MCU rows (1 .. 1024), 7 restart interval in MCUs
+ * (0: none), 8 .. 10 first block of each component's plane in coef (ep24_jpeg_fdct's cumulative block index), 11 .. 15 0}, row n =
+ * {total_blocks, total_segments}.
+ * ep24_jpeg_huffenc_count: positions[total_blocks] int64 receives, per block in scan order, the bits of the image's blocks up to and
+ *   including it; segments[total_segments][2] int64 = {first 32-bit word of the segment relative to the image's first - every segment
+ *   starts on a fresh word -, its bits without the 1-padding}; image_words[n] the words of every image, word_base[n + 1] their exclusive
+ *   sum: what the caller reads back (ONE synchronisation) to allocate words[word_base[n]], zeroed.  Three launches.
+ * ep24_jpeg_huffenc_emit: the same inputs and the count's outputs; every block's codes are shifted into words (big-endian; a word a block
+ *   fills entirely is a plain store, its first and last word are ORed in with atomicOr - words MUST be zero), then image_bytes[n] (the
+ *   stuffed bytes of every image, markers included), offsets[n + 1] (their exclusive sum) and out[offsets[i], offsets[i + 1]) are
+ *   written: the caller reads offsets and copies only [0, offsets[n]).  out_bytes >= 8 * nwords + 2 * total_segments always suffices.
+ *   Four launches.
+ * status[n] int32, zeroed by the caller in front of the count: bits are ORed in - 1 a DC difference outside +-2047, 2 an AC coefficient
+ *   outside +-1023 (nothing further of that block is coded; the image's bytes are then not a valid scan), 4 a store at or beyond nwords /
+ *   out_bytes was dropped - or EP24_E_ARG is written: a descriptor row that does not fit the buffers, nothing of that image is read or
+ *   written.  All positions are 64-bit.  No image index sits in a grid dimension's limit.
+ * EP24_E_ARG: a negative count, a null pointer with work to do, a misaligned buffer (coef 16 bytes, descriptors and sums 8, words and
+ * status 4); n = 0 launches nothing. */
+int ep24_jpeg_huffenc_count(const void* coef, int64_t ncoef, const int64_t* image_desc, int n, int64_t total_blocks, int64_t total_segments,
+                            int64_t* positions, int64_t* segments, int64_t* image_words, int64_t* word_base, int32_t* status, void* stream);
+int ep24_jpeg_huffenc_emit(const void* coef, int64_t ncoef, const int64_t* image_desc, int n, int64_t total_blocks, int64_t total_segments,
+                           const int64_t* positions, const int64_t* segments, const int64_t* word_base, uint32_t* words, int64_t nwords,
+                           int64_t* image_bytes, int64_t* offsets, uint8_t* out, int64_t out_bytes, int32_t* status, void* stream);
+
 /* Training augmentation (mosaic, random affine, mixup, mirror, HSV), two launches per batch.  Every output image
  * is assembled from up to four TILES: a tile is one source image, resized by s = min(S_h/h, S_w/w) as preproc resizes it and
  * placed on a canvas (2 S_h x 2 S_w with four tiles for a mosaic; S_h x S_w with one tile at the top left without).  Shared inputs:

@@ -106,6 +106,19 @@ int64_t ep24jpeg_encode_bound(const ep24jpeg_header* header);
 int ep24jpeg_entropy_encode(const ep24jpeg_header* header, const int16_t* coef, int64_t ncoef, uint8_t* out, int64_t capacity,
                             int64_t* nbytes);
 
+/* The bytes ep24jpeg_entropy_encode writes in front of the entropy-coded data: SOI up to and including the SOS header (it calls this
+ * routine's text).  *nbytes: their count (below 1 KiB).  EP24JPEG_E_ARG: a header ep24jpeg_entropy_encode refuses, or capacity below
+ * the count.  What the device encoder (ep24_jpeg_huffenc_count / _emit of libep24.so) leaves to the host, with the final FF D9. */
+int ep24jpeg_encode_header(const ep24jpeg_header* header, uint8_t* out, int64_t capacity, int64_t* nbytes);
+
+/* The device encoder with threads as loops (csrc/jpeg_huffenc_core.h is the text both run; DESIGN.md, "JPEG encode: Huffman stage on
+ * the GPU"): count every block's bits, sum them into positions (every restart segment on a fresh 32-bit word), emit every block at its
+ * position by ORing into zeroed words - the tiles of `tile` blocks (1 .. 2^20) last first, and the blocks of a tile last first - then
+ * count, sum and scatter the stuffed bytes in chunks of 64 unstuffed bytes, last chunk first.  Arguments, output and codes as
+ * ep24jpeg_entropy_encode, byte for byte. */
+int ep24jpeg_encode_emulate(const ep24jpeg_header* header, const int16_t* coef, int64_t ncoef, int tile, uint8_t* out, int64_t capacity,
+                            int64_t* nbytes);
+
 #ifdef __cplusplus
 }
 #endif
