@@ -15,7 +15,7 @@ inline unsigned grid_for(long n) { long b = (n + NTH - 1) / NTH; return (unsigne
 __device__ __forceinline__ float act_fwd_f32(float u, int act) {
     if (act == 1) return u / (1.f + expf(-u));                // x * sigmoid(x), full-precision expf and division
     if (act == 3) return u > 0.f ? u : 0.1f * u;
-    return act == 2 ? fmaxf(u, 0.f) : u;
+    return act == 2 ? (u < 0.f ? 0.f : u) : u;                // ReLU as ATen writes it: NaN stays NaN (fmaxf would hide it behind a 0)
 }
 __device__ __forceinline__ float act_grad_f32(float u, int act) {
     if (!act) return 1.f;
@@ -192,7 +192,8 @@ __global__ void bn_bwd_apply_f32_kernel(const float* dy, long ld_dy, const float
     }
 }
 
-// ---- SPP pools (5, 9, 13; stride 1; -inf padding), first maximum in row-major scan order like ATen
+// ---- SPP pools (5, 9, 13; stride 1; -inf padding), first maximum in row-major scan order like ATen, the last NaN if there is one;
+// a window with nothing above -inf points at its first cell
 __global__ void spp_fwd_f32_kernel(const float* x, long ld_x, float* y5, float* y9, float* y13, long ld_y, int* idx, int B, int H, int W, int C) {
     const long total = (long)B * H * W * C;
     for (long i = (long)blockIdx.x * NTH + threadIdx.x; i < total; i += (long)gridDim.x * NTH) {
@@ -211,7 +212,7 @@ __global__ void spp_fwd_f32_kernel(const float* x, long ld_x, float* y5, float* 
                 for (int xx = px - r; xx <= px + r; ++xx) {
                     if (xx < 0 || xx >= W) continue;
                     const float v = x[(((long)n * H + yy) * W + xx) * ld_x + c];
-                    if (v > best || arg < 0) { best = v; arg = yy * W + xx; }
+                    if (v > best || v != v || arg < 0) { best = v; arg = yy * W + xx; }      // a NaN always wins: the last one stays
                 }
             }
             outs[k][pix * ld_y + c] = best;
@@ -369,6 +370,7 @@ extern "C" int ep24_f32_bn_act_bwd(const float* dy, int64_t ld_dy, const float* 
                                    const float* beta, double* sums, float* gamma_grad, float* beta_grad, float* dz, int64_t ld_dz, int64_t M,
                                    int C, int act, void* stream) {
     EP24_REQUIRE(dy && z && save && gamma && beta && sums && dz && M > 0 && C > 0, EP24_E_ARG, "f32_bn_act_bwd: bad arguments");
+    EP24_REQUIRE(!gamma_grad == !beta_grad, EP24_E_ARG, "f32_bn_act_bwd: gamma_grad and beta_grad go together (both or neither)");
     hipLaunchKernelGGL(bn_bwd_reduce_f32_kernel, dim3(C), dim3(NTH), 0, S_, dy, ld_dy, z, ld_z, save, gamma, beta, sums, (long)M, C, act);
     F32_LAUNCH(bn_bwd_apply_f32_kernel, (long)M * C, dy, ld_dy, z, ld_z, save, gamma, beta, sums, gamma_grad, beta_grad, dz, ld_dz, (long)M, C, act);
     EP24_LAUNCH_CHECK("ep24_f32_bn_act_bwd");

@@ -283,12 +283,13 @@ int ep24_f32_conv_wgrad(const float* x, int64_t ld_x, const float* dy, int64_t l
 int ep24_f32_bn_act_fwd(const float* z, int64_t ld_z, const float* gamma, const float* beta, float* running_mean, float* running_var,
                         int64_t* num_batches, float* save, float* y, int64_t ld_y, const float* residual, int64_t ld_res, int64_t M,
                         int C, float eps, float momentum, int act, void* stream);
-/* both passes of its backward: sums [2C] double scratch; gamma_grad / beta_grad += ; dz written. */
+/* both passes of its backward: sums [2C] double scratch; gamma_grad / beta_grad += (both, or both null: EP24_E_ARG for one alone);
+ * dz written. */
 int ep24_f32_bn_act_bwd(const float* dy, int64_t ld_dy, const float* z, int64_t ld_z, const float* save, const float* gamma,
                         const float* beta, double* sums, float* gamma_grad, float* beta_grad, float* dz, int64_t ld_dz, int64_t M,
                         int C, int act, void* stream);
 int ep24_f32_spp_fwd(const float* x, int64_t ld_x, float* y5, float* y9, float* y13, int64_t ld_y, int32_t* idx, int B, int H, int W,
-                     int C, void* stream);                                        /* idx [3][B*H*W*C]: argmax pixel (y*W+x) */
+                     int C, void* stream);      /* idx [3][B*H*W*C]: argmax pixel (y*W+x): the first maximum, the last NaN if there is one */
 int ep24_f32_spp_bwd(const float* dy5, const float* dy9, const float* dy13, int64_t ld_dy, const int32_t* idx, float* dx,
                      int64_t ld_dx, int accumulate, int B, int H, int W, int C, void* stream);
 int ep24_f32_upsample2_fwd(const float* x, int64_t ld_x, float* y, int64_t ld_y, int B, int H, int W, int C, void* stream);
