@@ -120,8 +120,9 @@ def sort_records(key, cls, low_bits, cls_bits):
 
 class Evaluator24:
     """``Evaluator24(num_classes, iou_type="circle24", max_dets=100, conf_thre=0.01, nms_thre=0.65, nms_iou="rect",
-    max_candidates=None)``.  ``nms_iou`` / ``max_candidates`` are ``ep24.infer.postprocess``'s: ``"poly24"`` lets ``update``
-    suppress by the polygons' area IoU (class-aware, as its rectangle NMS is).
+    max_candidates=None, vote_thre=None)``.  ``nms_iou`` / ``max_candidates`` / ``vote_thre`` are ``ep24.infer.postprocess``'s:
+    ``"poly24"`` lets ``update`` suppress by the polygons' area IoU (class-aware, as its rectangle NMS is); with a ``vote_thre``
+    (polygon voting, ``nms_iou="poly24"`` only) ``update`` is ``update_detections(postprocess(..., vote_thre=...))``.
 
     ``update(predictions, labels)``: decoded eval-mode predictions [B, A, 27 + C] (the evaluator runs post_prepare +
     post_nms itself) and the label table [B, L, 51]; ``update_detections(dets, labels)``: ``ep24.infer.postprocess`` output.
@@ -129,10 +130,10 @@ class Evaluator24:
     ``AP50``, ``AP75``, ``AR100``, ``per_class_AP`` and the tables; ``summary`` holds the printed form."""
 
     def __init__(self, num_classes, iou_type="circle24", max_dets=100, conf_thre=0.01, nms_thre=0.65, device=None, nms_iou="rect",
-                 max_candidates=None):
-        from .infer import check_nms_iou
-        check_nms_iou(nms_iou, max_candidates)
-        self.nms_iou, self.max_candidates = nms_iou, max_candidates
+                 max_candidates=None, vote_thre=None):
+        from .infer import check_vote
+        check_vote(nms_iou, max_candidates, vote_thre)
+        self.nms_iou, self.max_candidates, self.vote_thre = nms_iou, max_candidates, vote_thre
         if not 0 < int(num_classes) < 0xFFFF:
             raise Ep24Error("ep24: Evaluator24 takes 1 .. 65534 classes, got %d (EP24_E_UNSUPPORTED)" % num_classes)
         if not 0 < int(max_dets) <= MAX_DETS:
@@ -185,6 +186,10 @@ class Evaluator24:
             self.seq += B
             return
         from . import infer
+        if self.vote_thre is not None:                    # the voted rows are no rows of `pred`: the evaluator takes them as a table
+            self.update_detections(infer.postprocess(pred, C, self.conf_thre, self.nms_thre, False, self.nms_iou, self.max_candidates,
+                                                     self.vote_thre), lab)
+            return
         key = (B, A, str(pred.device))
         ws = infer._scratch.get(key)
         if ws is None:

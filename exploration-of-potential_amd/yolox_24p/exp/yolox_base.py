@@ -73,6 +73,9 @@ class Exp(BaseExp):
         self.eval_seed = 1               # its own seed: the training source uses 0
         self.eval_iou_type = "circle24"  # ep24.evaluate: "circle24" (the model's geometry), "rect" (bounding boxes) or "poly24" (polygon area)
         self.nms_iou_type = "rect"       # NMS of the evaluation: "rect" (the reference's rectangle rule) or "poly24" (the polygons' area IoU)
+        self.eval_tta = False            # test-time augmentation of the evaluation (ep24.tta): needs nms_iou_type "poly24"
+        self.eval_tta_scales = (1.0, 0.85, 0.7)   # its views: each scale of test_size, plain and mirrored, the canonical one first
+        self.eval_vote = None            # polygon voting: the voters' IoU threshold, or None (needs nms_iou_type "poly24")
 
     def get_model(self):
         from models import YOLOX, YOLOPAFPN, YOLOXHead
@@ -206,8 +209,14 @@ class Exp(BaseExp):
         from ep24.evaluate import Evaluator24
         if is_distributed:
             raise Ep24Error("ep24: distributed evaluation (gathering records across ranks) is not implemented")
+        max_candidates = None
+        if getattr(self, "eval_tta", False):
+            # the merged table holds every view's anchors; only the canonical view's count of them enters the polygon NMS, so that
+            # the suppression matrix keeps the size it has without the views
+            from ep24.tta import anchors_for
+            max_candidates = anchors_for(tuple(self.test_size))
         evaluator = Evaluator24(self.num_classes, iou_type=self.eval_iou_type, conf_thre=self.test_conf, nms_thre=self.nmsthre,
-                                nms_iou=self.nms_iou_type)
+                                nms_iou=self.nms_iou_type, max_candidates=max_candidates, vote_thre=getattr(self, "eval_vote", None))
         evaluator.dataloader = self.get_eval_loader(batch_size)
         return evaluator
 
@@ -222,6 +231,10 @@ class Exp(BaseExp):
         if half:
             raise Ep24Error("ep24: the eval-mode network runs in bf16 with fp32 outputs; half=True is not a separate mode")
         transform = TrainTransform(max_labels=50)
+        views = None
+        if getattr(self, "eval_tta", False):
+            from ep24 import tta
+            views = tta.views_for(tuple(self.test_size), self.eval_tta_scales)
         was_training = model.training
         model.eval()
         evaluator.reset()
@@ -229,9 +242,12 @@ class Exp(BaseExp):
             with torch.no_grad():
                 for images, targets, _, _ in evaluator.dataloader:
                     imgs, labs = transform.batch(images, targets, tuple(self.test_size))
-                    evaluator.update(model(imgs, train=False), labs)
+                    evaluator.update(model(imgs, train=False) if views is None else tta.predict(model, imgs, views), labs)
             stats = evaluator.summarize()
         finally:
+            if views is not None:
+                torch.cuda.synchronize()
+                tta.release(model)                        # the views' eval plans go with the evaluation
             if was_training:
                 model.train()
         return stats["AP"], stats["AP50"], evaluator.summary

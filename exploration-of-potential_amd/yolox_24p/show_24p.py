@@ -195,8 +195,14 @@ class Evaluator:
             names = self.file_list[lo:lo + step]
             originals = [torch.from_numpy(read_image(os.path.join(self.folder, f))).to(self.device) for f in names]
             images, ratios = preproc_batch(originals, self.input_size, device=self.device)
-            outputs = postprocess(model(images, train=False), self.num_classes, conf_thre=args.conf, nms_thre=args.nms,
-                                  nms_iou=args.nms_iou)
+            if getattr(args, "tta", False):
+                # every view of ep24.tta.views_for, merged; polygon NMS over the canonical view's anchor count of candidates
+                from ep24 import tta
+                outputs = tta.postprocess(tta.predict(model, images), self.num_classes, tta.anchors_for(self.input_size),
+                                          conf_thre=args.conf, nms_thre=args.nms, vote_thre=getattr(args, "vote", None))
+            else:
+                outputs = postprocess(model(images, train=False), self.num_classes, conf_thre=args.conf, nms_thre=args.nms,
+                                      nms_iou=args.nms_iou, vote_thre=getattr(args, "vote", None))
             drawn_batch = []
             for name, img, ratio, dets in zip(names, originals, ratios, outputs):
                 drawn = draw_detections(img, dets, ratio=ratio, conf=args.draw_conf, num_classes=self.num_classes,
@@ -214,7 +220,7 @@ class Evaluator:
                          getattr(args, "jpeg_entropy", "host"))
         with open(os.path.join(self.save_folder, "detections.json"), "w") as fh:
             json.dump({"input_size": list(self.input_size), "conf": args.conf, "nms": args.nms, "nms_iou": args.nms_iou,
-                       "draw_conf": args.draw_conf, "images": records}, fh, indent=1)
+                       "tta": bool(getattr(args, "tta", False)), "vote": getattr(args, "vote", None), "draw_conf": args.draw_conf, "images": records}, fh, indent=1)
         if segm is not None:
             segm.dump(args.save_segm)
             print("saved %d segm results to %s" % (len(segm), args.save_segm))
@@ -222,8 +228,42 @@ class Evaluator:
         return self.save_folder
 
 
+class _NmsIouAction(argparse.Action):
+    """--nms-iou, remembering that it was given: --tta implies poly24 and refuses an explicit rect."""
+
+    def __call__(self, parser, namespace, values, option_string=None):
+        setattr(namespace, self.dest, values)
+        namespace.nms_iou_given = True
+
+
+def check_tta_args(args):
+    """--tta implies --nms-iou poly24 (and refuses an explicit rect); --vote T >= 0 needs the polygon NMS.  Returns the message of
+    the refusal, or None."""
+    given = getattr(args, "nms_iou_given", False)
+    if getattr(args, "tta", False):
+        if given and args.nms_iou != "poly24":
+            return "--tta merges the views by the polygon NMS: it implies --nms-iou poly24 (got --nms-iou %s)" % args.nms_iou
+        args.nms_iou = "poly24"
+    vote = getattr(args, "vote", None)
+    if vote is not None:
+        if args.nms_iou != "poly24":
+            return "--vote finds its voters in the buffers of the polygon NMS: add --nms-iou poly24 or --tta"
+        if not vote >= 0.0:
+            return "--vote %r: the IoU threshold of the voters, at least 0" % vote
+    return None
+
+
+class _Parser(argparse.ArgumentParser):
+    def parse_args(self, args=None, namespace=None):
+        a = super().parse_args(args, namespace)
+        msg = check_tta_args(a)
+        if msg:
+            self.error(msg)
+        return a
+
+
 def make_parser():
-    p = argparse.ArgumentParser("YOLOX show parser")
+    p = _Parser("YOLOX show parser")
     p.add_argument("-b", "--batch_size", type=int, default=64, help="batch size")
     p.add_argument("-s", "--start_device", default=0, type=int, help="device for start count")
     p.add_argument("-d", "--devices", default=1, type=int, help="number of devices (one is used)")
@@ -234,8 +274,13 @@ def make_parser():
     p.add_argument("--output-dir", default=None, type=str, help="results go to <output-dir>/<timestamp>/ (default: exp.output_dir)")
     p.add_argument("--conf", default=0.01, type=float, help="postprocess: obj * class_conf threshold (the reference's 0.01)")
     p.add_argument("--nms", default=0.3, type=float, help="postprocess: NMS IoU threshold (the reference's 0.3)")
-    p.add_argument("--nms-iou", default="rect", choices=["rect", "poly24"], help="NMS by the reference's rectangles or by the "
-                   "exact area IoU of the 24-point polygons")
+    p.add_argument("--nms-iou", default="rect", choices=["rect", "poly24"], action=_NmsIouAction, help="NMS by the reference's "
+                   "rectangles or by the exact area IoU of the 24-point polygons")
+    p.add_argument("--tta", action="store_true", help="test-time augmentation (ep24.tta): every batch also at 0.85 and 0.7 of the input "
+                   "size, each size plain and mirrored, the predictions brought back into one frame and merged by the polygon NMS "
+                   "(implies --nms-iou poly24); one forward per view")
+    p.add_argument("--vote", default=None, type=float, metavar="T", help="polygon voting: every kept detection becomes the score-weighted "
+                   "consensus of the candidates whose area IoU with it is above T (needs --nms-iou poly24 or --tta)")
     p.add_argument("--draw-conf", default=1e-4, type=float, help="detections below this score are not drawn (the reference's 0.0001)")
     p.add_argument("--fill-alpha", default=0, type=int, help="0..255: blend the class colour over the polygon's inside (0 = outline only)")
     p.add_argument("--show-scores", action="store_true", help="append the score's two decimals to the label")

@@ -77,6 +77,8 @@ class Trainer:
             raise SystemExit("train_24p.py: --augment works on the raw uint8 batches behind the prefetcher (drop --no-prefetch / --fp32-batches)")
         check_mixup_args(args)
         check_copy_paste_args(args)
+        if check_eval_tta_args(args):
+            raise SystemExit("train_24p.py: " + check_eval_tta_args(args))
         check_multiscale_args(args, exp, self.world)
         if args.fisheye_theta is not None:
             check_fisheye_args(args)
@@ -479,8 +481,58 @@ def check_fisheye_args(args):
 EXP_VALUE = object()       # --weight-decay without a value (not a string: argparse would hand it to float())
 
 
+def check_eval_tta_args(args):
+    """--eval-tta implies --nms-iou poly24 (an explicit rect is refused); --eval-vote T >= 0 needs the polygon NMS, named by
+    --nms-iou poly24 or implied by --eval-tta; --eval-tta-scales belongs to --eval-tta and starts with the canonical 1.0.
+    Returns the message of the refusal, or None."""
+    tta = getattr(args, "eval_tta", False)
+    nms_iou = getattr(args, "nms_iou", None)
+    if tta and nms_iou not in (None, "poly24"):
+        return "--eval-tta merges the views by the polygon NMS: it implies --nms-iou poly24 (got --nms-iou %s)" % nms_iou
+    scales = getattr(args, "eval_tta_scales", None)
+    if scales is not None:
+        if not tta:
+            return "--eval-tta-scales names the views of --eval-tta (add --eval-tta)"
+        if float(scales[0]) != 1.0 or any(not 0.0 < float(s) <= 1.0 for s in scales):
+            return "--eval-tta-scales %s: the canonical view 1.0 first, then scales in (0, 1]" % (scales,)
+    vote = getattr(args, "eval_vote", None)
+    if vote is not None:
+        if not tta and nms_iou != "poly24":
+            return "--eval-vote finds its voters in the buffers of the polygon NMS: add --nms-iou poly24 or --eval-tta"
+        if not vote >= 0.0:
+            return "--eval-vote %r: the IoU threshold of the voters, at least 0" % vote
+    return None
+
+
+def apply_eval_args(exp, args):
+    """The evaluation flags on the Exp: --eval-iou, --nms-iou, --eval-tta (with its scales; implies the polygon NMS), --eval-vote."""
+    msg = check_eval_tta_args(args)
+    if msg:
+        raise SystemExit("train_24p.py: " + msg)
+    if getattr(args, "eval_iou", None) is not None:
+        exp.eval_iou_type = args.eval_iou
+    if getattr(args, "nms_iou", None) is not None:
+        exp.nms_iou_type = args.nms_iou
+    if getattr(args, "eval_tta", False):
+        exp.eval_tta = True
+        exp.nms_iou_type = "poly24"
+        if getattr(args, "eval_tta_scales", None) is not None:
+            exp.eval_tta_scales = tuple(float(s) for s in args.eval_tta_scales)
+    if getattr(args, "eval_vote", None) is not None:
+        exp.eval_vote = float(args.eval_vote)
+
+
+class _Parser(argparse.ArgumentParser):
+    def parse_args(self, args=None, namespace=None):
+        a = super().parse_args(args, namespace)
+        msg = check_eval_tta_args(a)
+        if msg:
+            self.error(msg)
+        return a
+
+
 def make_parser():
-    p = argparse.ArgumentParser("YOLOX train parser")
+    p = _Parser("YOLOX train parser")
     p.add_argument("-b", "--batch_size", type=int, default=4, help="batch size (per GPU)")
     p.add_argument("-l", "--learn_rate", type=float, default=0.001, help="learn rate")
     p.add_argument("-s", "--start_device", default=0, type=int, help="device for start count")
@@ -553,16 +605,21 @@ def make_parser():
                    "overrides the Exp's eval_iou_type; poly24 is the exact area IoU of the 24-point polygons")
     p.add_argument("--nms-iou", default=None, choices=["rect", "poly24"], help="NMS of the evaluation: overrides the Exp's nms_iou_type; "
                    "rect is the reference's rectangle rule, poly24 suppresses by the exact area IoU of the 24-point polygons")
+    p.add_argument("--eval-tta", action="store_true", help="test-time augmentation of the evaluation (ep24.tta): every batch at each of "
+                   "--eval-tta-scales, plain and mirrored, the predictions brought back into one frame and merged by the polygon NMS "
+                   "(implies --nms-iou poly24) over the canonical view's anchor count of candidates; one forward per view")
+    p.add_argument("--eval-tta-scales", default=None, type=float, nargs="+", metavar="S", help="with --eval-tta: the views' scales, 1.0 "
+                   "first (default: the Exp's eval_tta_scales, 1.0 0.85 0.7); each must keep the height a multiple of 32")
+    p.add_argument("--eval-vote", default=None, type=float, metavar="T", help="polygon voting in the evaluation: every kept detection "
+                   "becomes the score-weighted consensus of the candidates whose area IoU with it is above T (needs --nms-iou poly24 "
+                   "or --eval-tta)")
     return p
 
 
 def main(exp, args):
     if args.output_dir:
         exp.output_dir = args.output_dir
-    if getattr(args, "eval_iou", None) is not None:
-        exp.eval_iou_type = args.eval_iou
-    if getattr(args, "nms_iou", None) is not None:
-        exp.nms_iou_type = args.nms_iou
+    apply_eval_args(exp, args)
     if args.synthetic_len:
         exp.synthetic_len = args.synthetic_len
     for name in ("data_dir", "label_dir", "val_data_dir", "val_label_dir", "jpeg_decoder"):

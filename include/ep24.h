@@ -625,6 +625,26 @@ int ep24_post_nms_poly24(const float* pred, int ncols, const float* score, const
                          float nms_thre, int class_agnostic, const float* ray_cs, float* sort_key, int32_t* sort_idx, int P,
                          int32_t* n_cand, float* verts, float* vbox, int32_t* vcls, uint64_t* mask, int32_t* keep,
                          int32_t* keep_count, void* stream);
+/* Polygon voting (csrc/tta.hip; DESIGN.md section 7, "Test-time augmentation"): runs after ep24_post_nms_poly24 on the buffers
+ * that call leaves behind (sort_idx, n_cand, verts, vbox, vcls, keep, keep_count; same B, A, K, P, pred, score) and
+ * replaces every kept detection by the score-weighted consensus of its voters.  voted [B][A][26] fp32: row m of image b belongs
+ * to keep[b][m]; rows at and beyond keep_count[b] are not written.  n_voters [B][A] int32 likewise.
+ *   Voters of the kept sorted row i: every sorted candidate j < n_cand[b], ranked before or after i, with the same class (unless
+ *   class_agnostic) and poly24_iou(a = P_i, b = P_j) > (double)vote_thre - ep24_eval_iou's orientation with the kept row as the
+ *   GT side - and i itself, always.  Pairs whose fp32 vertex boxes do not overlap have IoU exactly 0.0 and are not evaluated: exact
+ *   for vote_thre >= 0; a negative (or NaN) vote_thre is EP24_E_ARG.  A NaN IoU never votes.
+ *   One voter, or voters whose scores sum to 0: the 26 values of the kept row, bit for bit.  Otherwise, all in double with
+ *   w_j = score[b][row_j]: C = sum w_j c_j / sum w_j over the voters' centres (pred columns 0, 1); for ray k, t_jk = the nearest
+ *   crossing t >= 0 of C + t * (cos, sin)(15 deg * k) - the direction in double - with the closed polygon verts_j by the side-of-line rule of
+ *   ep24_augment_labels (an edge counts iff its ends' side values have opposite signs or are zero; one side value per vertex;
+ *   an edge on the line gives its ends), a voter without a crossing abstains on that ray, r_k = sum w_j t_jk / sum w_j over the
+ *   others, and the kept row's own r_k when that weight is not positive.  C and r_k are rounded once to fp32.  Every sum has a
+ *   fixed order; no floating-point atomics.  The grid follows from B and K alone; no host synchronisation.
+ *   EP24_E_ARG / EP24_E_UNSUPPORTED as ep24_post_nms_poly24. */
+int ep24_post_vote_poly24(const float* pred, int ncols, const float* score, int B, int A, int K, float vote_thre,
+                          int class_agnostic, const int32_t* sort_idx, int P, const int32_t* n_cand,
+                          const float* verts, const float* vbox, const int32_t* vcls, const int32_t* keep,
+                          const int32_t* keep_count, float* voted, int32_t* n_voters, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * E1  evaluation: COCO-style AP of 24-point detections (pycocotools evaluateImg + accumulate, area "all", no crowd /
@@ -934,6 +954,18 @@ int ep24_resize_bilinear_f32(const float* src, int n, int sh, int sw, float* dst
 /* The label half: rows x 51 floats; column 0 (the class) copied, odd columns * scale_x, even columns >= 2 * scale_y (one rounded fp32
  * multiply each: targets[..., 1::2] * scale_x, targets[..., 2::2] * scale_y).  out == in is allowed.  rows <= 2^40. */
 int ep24_scale_labels(const float* in, float* out, int64_t rows, float scale_x, float scale_y, void* stream);
+/* Test-time augmentation (csrc/tta.hip, ep24/tta.py).  ep24_mirror_f32: N planes [H][W] of fp32 mirrored left to right,
+ * out[n][y][x] = in[n][y][W - 1 - x] as 32-bit words (NaN payloads stay); any W >= 1, 16-byte accesses when W % 4 == 0 and both
+ * pointers are 16-byte aligned.  in == out is EP24_E_ARG. */
+int ep24_mirror_f32(const float* in, int N, int H, int W, float* out, void* stream);
+/* The B x A_v decoded prediction rows view[B][A_v][ncols] of one view of width w_v, brought back into the canonical frame and
+ * written to rows [off, off + A_v) of every image of merged[B][A_tot][ncols]; other rows are not touched.  s = the fp32 value of
+ * W0 / w_v, computed by the host in double and rounded once.  Each operation is one fp32 operation: cx' = cx * s, or
+ * (w_v - cx) * s when mirror (the label mirror's W - x); cy' = cy * s; r'_k = r_k * s, or r_((12 - k) mod 24) * s when mirror.
+ * Columns >= 26 are copied as words; with s == 1.0f and mirror == 0 the whole row is.  EP24_E_ARG: ncols < 27, off < 0,
+ * off + A_v > A_tot, s not finite or not positive. */
+int ep24_tta_unmap(const float* view, int B, int A_v, int ncols, int w_v, float s, int mirror, float* merged, int A_tot, int off,
+                   void* stream);
 
 /* Baseline JPEG decode, the arithmetic half ("JPEG decode"): what libjpeg's default path computes behind its Huffman stage
  * - dequantisation, the islow integer IDCT, "fancy" chroma upsampling, 16-bit fixed-point YCbCr -> RGB, clamp - bit for bit, for a
