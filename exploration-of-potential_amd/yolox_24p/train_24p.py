@@ -82,6 +82,7 @@ class Trainer:
         check_multiscale_args(args, exp, self.world)
         if args.fisheye_theta is not None:
             check_fisheye_args(args)
+        check_fisheye_lens_args(args)
         self.train_loader = exp.get_data_loader(args.batch_size, raw_u8=bool(args.raw_u8), workers=args.loader_workers,
                                                  pin=None if args.loader_pin is None else bool(args.loader_pin))
         self.loss_func = Loss_Function(exp.num_classes)
@@ -326,6 +327,8 @@ class Trainer:
             pf = DataPrefetcher(self.positioned(self.train_loader), tuple(self.input_size), self.augment_transform())
         elif self.args.fisheye_theta is not None:
             pf = DataPrefetcher(self.positioned(self.train_loader), tuple(self.input_size), self.fisheye_transform())
+        elif getattr(self.args, "fisheye_lens", None):
+            pf = DataPrefetcher(self.positioned(self.train_loader), tuple(self.input_size), self.lens_transform())
         else:
             pf = DataPrefetcher(self.train_loader, tuple(self.input_size), TrainTransform(max_labels=50))
         self.prefetcher = pf                              # its t_loader / t_upload split the throughput record's host time
@@ -363,6 +366,21 @@ class Trainer:
         if getattr(self, "transform", None) is None:
             from ep24.fisheye import FisheyeTransform
             self.transform = FisheyeTransform(theta=tuple(self.args.fisheye_theta), max_labels=50, seed=self.args.augment_seed)
+        return self.transform
+
+    def lens_transform(self):
+        """--fisheye-lens FILE [FILE ...]: ONE ``LensTransform`` for the run - every image and its 24-point labels as one of the
+        calibrated lenses sees them (ep24.lens), a lens drawn per image.  A file's ``size`` says which frame its intrinsics are for;
+        without one they are taken as given for the Exp's input_size."""
+        if getattr(self, "transform", None) is None:
+            from ep24.lens import LensModel, LensTransform
+            models = []
+            for path in self.args.fisheye_lens:
+                m = LensModel.from_json(path)
+                if m.size is None:
+                    m.size = (int(self.exp.input_size[0]), int(self.exp.input_size[1]))
+                models.append(m)
+            self.transform = LensTransform(models, max_labels=50, seed=self.args.augment_seed)
         return self.transform
 
     def positioned(self, loader):
@@ -476,6 +494,21 @@ def check_fisheye_args(args):
         raise SystemExit("train_24p.py: --fisheye-theta works on the raw uint8 batches behind the prefetcher (drop --no-prefetch / --fp32-batches)")
     if not 15 <= lo <= hi <= 180:
         raise SystemExit("train_24p.py: --fisheye-theta LO HI needs 15 <= LO <= HI <= 180")
+
+
+def check_fisheye_lens_args(args):
+    """--fisheye-lens works on the raw uint8 batches, one warp per run, and the lens is not composed with mosaic / affine."""
+    if not getattr(args, "fisheye_lens", None):
+        return
+    if args.fisheye_theta is not None:
+        raise SystemExit("train_24p.py: --fisheye-lens and --fisheye-theta exclude each other (a calibrated lens or the sector warp, not both)")
+    if args.augment:
+        raise SystemExit("train_24p.py: --fisheye-lens and --augment exclude each other (the lens model is not composed with mosaic / affine)")
+    if args.no_prefetch or args.fp32_batches or not getattr(args, "raw_u8", True):
+        raise SystemExit("train_24p.py: --fisheye-lens works on the raw uint8 batches behind the prefetcher (drop --no-prefetch / --fp32-batches)")
+    for path in args.fisheye_lens:
+        if not os.path.isfile(path):
+            raise SystemExit("train_24p.py: --fisheye-lens %s: no such calibration file (JSON: K, D, pinhole, fov_deg, size)" % path)
 
 
 EXP_VALUE = object()       # --weight-decay without a value (not a string: argparse would hand it to float())
@@ -599,6 +632,10 @@ def make_parser():
     p.add_argument("--fisheye-theta", default=None, type=int, nargs=2, metavar=("LO", "HI"), help="fisheye sector warp of every image AND its "
                    "24-point labels on the GPU (ep24.fisheye.FisheyeTransform behind the prefetcher), one angle in [LO, HI] degrees per image, "
                    "reproducible from (--augment-seed, epoch, iteration); not together with --augment")
+    p.add_argument("--fisheye-lens", default=None, nargs="+", metavar="FILE", help="calibrated fisheye lens (JSON of numbers: K 3x3 and D 4 in "
+                   "OpenCV's cv2.fisheye layout, pinhole, fov_deg, size): every image AND its 24-point labels as the lens sees them, on the GPU "
+                   "(ep24.lens.LensTransform behind the prefetcher); with several files one lens is drawn per image, reproducible from "
+                   "(--augment-seed, epoch, iteration); not together with --fisheye-theta or --augment")
     p.add_argument("--eval-interval", default=0, type=int, help="every N epochs: COCO-style AP (exp.eval, ep24.evaluate) of the EMA model "
                    "(--ema) or the model, logged and saved as best_ckpt.pth when it improves (0 = off; single process only)")
     p.add_argument("--eval-iou", default=None, choices=["circle24", "rect", "poly24"], help="IoU type of the evaluation (ep24.evaluate): "

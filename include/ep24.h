@@ -563,6 +563,52 @@ int ep24_sector_labels(const double* rows, const double* geo, const double* rot,
                        float* out, int32_t* out_count, int32_t* out_flags, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * a13b  fisheye lens model (Kannala-Brandt, the model of OpenCV's cv2.fisheye): images, points, labels by calibration
+ * ------------------------------------------------------------------------------------------------ */
+/* A lens is model[14] float64: pin = (fx, fy, cx, cy) of the pinhole frame, fish = (fx, fy, cx, cy) of the fisheye frame, k1..k4,
+ * theta_max (half field of view in radians, 0 < theta_max < pi / 2) and thetad(theta_max).  Coordinates are pixel-index coordinates
+ * (pixel i is centred at i, as for ep24_sector_points).  All map arithmetic is double, every operation rounded on its own, with
+ *     P(t) = 1 + t (k1 + t (k2 + t (k3 + t k4)))      thetad(th) = th * P(th^2)
+ * to_fisheye(u, v):   a = (u - cx_p) / fx_p, b = (v - cy_p) / fy_p, r = hypot(a, b);  th = min(atan r, theta_max);
+ *                     s = r > 0 ? thetad(th) / r : 1;   (X, Y) = (fx_f * a * s + cx_f, fy_f * b * s + cy_f)
+ * to_pinhole(X, Y):   x = (X - cx_f) / fx_f, y = (Y - cy_f) / fy_f, rd = hypot(x, y);  td = min(rd, thetad(theta_max));
+ *                     th solves thetad(th) = td: Newton from th = td, a fixed 12 steps th -= (thetad(th) - td) / thetad'(th) with
+ *                     thetad'(th) = 1 + t (3 k1 + t (5 k2 + t (7 k3 + t 9 k4))), t = th^2, clamped to [0, theta_max] after each;
+ *                     s = rd > 0 ? tan th / rd : 1;   (u, v) = (fx_p * x * s + cx_p, fy_p * y * s + cy_p)
+ *                     (the divisor is rd, as it is r above: inside the field rd = td, beyond it the point keeps its azimuth only)
+ * A point beyond the field lands on the field's rim at the same azimuth; nothing is ever non-finite.  k = 0 is the equidistant
+ * projection.  The host (ep24.lens.LensModel) refuses a model whose thetad is not increasing on [0, theta_max] or whose Newton
+ * iteration does not reproduce th to 1e-14; the entry points below take the table as it is.
+ * `direction`: 0 = distort (pinhole -> fisheye), 1 = undistort (fisheye -> pinhole).
+ *
+ * ep24_lens_points: points [m][2] and out [m][2] device float64 (x, y) through to_fisheye (0) or to_pinhole (1); `model` is a HOST
+ * pointer, read during the call; one thread per point; m == 0 is EP24_OK. */
+int ep24_lens_points(const double* points, int m, const double* model, int direction, double* out, void* stream);
+/* Images, one launch per batch.  images: one packed uint8 buffer; desc [n][3] int64 = {byte offset, h, w} of every contiguous HWC
+ * source (h, w < 2^26); table [n][18] float64 = {model[14], direction, dst_h, dst_w, byte offset of the image in `out`}.  Every
+ * destination pixel (ox, oy) is mapped into the source frame with the OTHER direction's map (distort: (sx, sy) = to_pinhole(ox, oy),
+ * undistort: to_fisheye).  It is SAMPLED when it lies inside the field (distort: hypot(x, y) <= thetad(theta_max); undistort:
+ * atan r <= theta_max) and 0 <= sx <= w - 1 and 0 <= sy <= h - 1, else it takes `fill` (0..255) in every channel.  The sample is
+ * bilinear in integers:  qx = floor(sx * 32 + 0.5), xa = qx >> 5, wx = qx & 31, xb = min(xa + 1, w - 1), the same for y, and
+ *     v = ((32 - wx)(32 - wy) p[ya][xa] + wx (32 - wy) p[ya][xb] + (32 - wx) wy p[yb][xa] + wx wy p[yb][xb] + 512) >> 10.
+ * ep24_lens_warp_u8 writes uint8 HWC images of any sizes into `out` at their offsets; max_pixels, the largest dst_h * dst_w of the
+ * batch, sizes the grid only: (min(ceil(max_pixels / 256), 4096), n) workgroups that stride over the pixels of their image.
+ * ep24_lens_preproc_u8 writes the network input, out [n][3][S_h][S_w] fp32 with the channel order kept and the values of the uint8
+ * form; the destination of every image is S_h x S_w (the table's size and offset fields are not read); the same grid rule with
+ * S_h * S_w pixels, which must stay below 2^31 - 2^20.  n == 0 is EP24_OK; n <= 65535. */
+int ep24_lens_warp_u8(const uint8_t* images, const int64_t* desc, const double* table, int n, int64_t max_pixels, uint8_t* out,
+                      int fill, void* stream);
+int ep24_lens_preproc_u8(const uint8_t* images, const int64_t* desc, const double* table, int n, float* out, int S_h, int S_w,
+                         int fill, void* stream);
+/* 24-point labels under the lens map: the contract of ep24_sector_labels, steps (a) - (e), with the forward map of the image's
+ * direction (distort: to_fisheye, undistort: to_pinhole) in place of the sector map.  geo [n][22] float64 per image: model[14],
+ * direction, h, w (the source image: rows are normalised by them), h', w' (the destination: vertices are clamped to
+ * [0, w'] x [0, h']), the scale that centre and vertices are multiplied by, index of the image's first row in `rows`, number of its
+ * rows.  Everything else as for ep24_sector_labels. */
+int ep24_lens_labels(const double* rows, const double* geo, const double* rot, int n, int max_labels, float* cand, int32_t* keep,
+                     float* out, int32_t* out_count, int32_t* out_flags, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * N3  inference path: eval-mode network + postprocess
  * ------------------------------------------------------------------------------------------------ */
 /* BaseConv in eval mode (network_blocks.py:50-51 with BatchNorm2d.eval()): y = act(z*scale + shift) (+ residual),
