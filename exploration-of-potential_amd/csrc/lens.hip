@@ -9,6 +9,7 @@
 // of the image, 256 threads.  Labels: labelwarp.h with the lens map in place of the sector map.
 #include "common.h"
 #include "labelwarp.h"
+#include "lensmath.h"
 
 namespace {
 
@@ -30,8 +31,7 @@ __device__ __forceinline__ void lens_to_fisheye(const Lens& L, double u, double 
     const double t = atan(r);
     in = t <= L.tmax;
     const double th = fmin(t, L.tmax);
-    const double t2 = th * th;
-    const double td = th * (1.0 + t2 * (L.k1 + t2 * (L.k2 + t2 * (L.k3 + t2 * L.k4))));
+    const double td = lens_thetad(th, L.k1, L.k2, L.k3, L.k4);
     const double s = r > 0.0 ? td / r : 1.0;
     X = L.ffx * a * s + L.fcx;
     Y = L.ffy * b * s + L.fcy;
@@ -44,15 +44,7 @@ __device__ __forceinline__ void lens_to_pinhole(const Lens& L, double X, double 
     const double rd = hypot(x, y);
     in = rd <= L.tdmax;
     const double td = fmin(rd, L.tdmax);
-    double th = td;
-#pragma unroll 1
-    for (int it = 0; it < 12; ++it) {
-        const double t2 = th * th;
-        const double f = th * (1.0 + t2 * (L.k1 + t2 * (L.k2 + t2 * (L.k3 + t2 * L.k4)))) - td;
-        const double fp = 1.0 + t2 * (3.0 * L.k1 + t2 * (5.0 * L.k2 + t2 * (7.0 * L.k3 + t2 * (9.0 * L.k4))));
-        th = th - f / fp;
-        th = fmin(fmax(th, 0.0), L.tmax);
-    }
+    const double th = lens_newton(td, L.k1, L.k2, L.k3, L.k4, L.tmax);
     const double s = rd > 0.0 ? tan(th) / rd : 1.0;              // rd, not td: a point beyond the field lands on its rim
     u = L.pfx * x * s + L.pcx;
     v = L.pfy * y * s + L.pcy;

@@ -76,6 +76,10 @@ class Exp(BaseExp):
         self.eval_tta = False            # test-time augmentation of the evaluation (ep24.tta): needs nms_iou_type "poly24"
         self.eval_tta_scales = (1.0, 0.85, 0.7)   # its views: each scale of test_size, plain and mirrored, the canonical one first
         self.eval_vote = None            # polygon voting: the voters' IoU threshold, or None (needs nms_iou_type "poly24")
+        self.eval_areas = False          # pycocotools' twelve lines: AP / AR by object size (small, medium, large), maxDets 1 / 10 / 100
+        self.eval_zones = None           # AP per distortion zone: "radius" (distance from the image centre) or "lens" (incidence angle)
+        self.eval_zone_edges = None      # the zones' edges; None: 0 1/3 2/3 inf (radius), 0 30 60 90 degrees (lens)
+        self.eval_lens = None            # "lens" zones: an ep24.lens.LensModel or its JSON file, the calibration of the validation images
 
     def get_model(self):
         from models import YOLOX, YOLOPAFPN, YOLOXHead
@@ -215,10 +219,49 @@ class Exp(BaseExp):
             # the suppression matrix keeps the size it has without the views
             from ep24.tta import anchors_for
             max_candidates = anchors_for(tuple(self.test_size))
-        evaluator = Evaluator24(self.num_classes, iou_type=self.eval_iou_type, conf_thre=self.test_conf, nms_thre=self.nmsthre,
-                                nms_iou=self.nms_iou_type, max_candidates=max_candidates, vote_thre=getattr(self, "eval_vote", None))
+        strata, max_dets = self.eval_strata()
+        evaluator = Evaluator24(self.num_classes, iou_type=self.eval_iou_type, max_dets=max_dets, conf_thre=self.test_conf,
+                                nms_thre=self.nmsthre, nms_iou=self.nms_iou_type, max_candidates=max_candidates,
+                                vote_thre=getattr(self, "eval_vote", None), strata=strata)
         evaluator.dataloader = self.get_eval_loader(batch_size)
         return evaluator
+
+    ZONE_EDGES = {"radius": (0.0, 1.0 / 3.0, 2.0 / 3.0, float("inf")), "lens": (0.0, 30.0, 60.0, 90.0)}
+
+    def eval_strata(self):
+        """``(strata, max_dets)`` of ``eval_areas`` / ``eval_zones`` / ``eval_zone_edges``: the four COCO area rows at maxDets
+        (1, 10, 100), then one stratum per zone; ``(None, 100)`` with none of them set - the evaluator as it was."""
+        from ep24 import evaluate as E
+        areas, zones = getattr(self, "eval_areas", False), getattr(self, "eval_zones", None)
+        if not areas and zones is None:
+            return None, 100
+        if zones not in (None, "radius", "lens"):
+            raise ValueError("eval_zones must be None, 'radius' or 'lens', got %r" % (zones,))
+        strata = E.coco_area_strata() if areas else [E.Stratum("all")]
+        if zones is not None:
+            if zones == "lens" and getattr(self, "eval_lens", None) is None:
+                raise ValueError("eval_zones 'lens' needs eval_lens: the calibration of the validation images")
+            edges = getattr(self, "eval_zone_edges", None) or self.ZONE_EDGES[zones]
+            strata = strata + E.zone_strata(edges, "r" if zones == "radius" else "deg")
+        return strata, ((1, 10, 100) if areas else 100)
+
+    def eval_tables(self, sizes):
+        """``(scales, zones)`` of a validation batch from its raw images' ``sizes`` (h, w) and ``test_size``: the letterbox ratios, and
+        the zone rows of ``eval_zones`` - for "lens" the calibration brought to ``test_size`` from its ``size`` (a file without one
+        is taken as given for ``test_size``), as the trainer's lens transform scales its models."""
+        from ep24 import evaluate as E
+        S = (int(self.test_size[0]), int(self.test_size[1]))
+        zones = getattr(self, "eval_zones", None)
+        zt = None
+        if zones == "radius":
+            zt = E.radius_zones(sizes, S)
+        elif zones == "lens":
+            from ep24.lens import LensModel, image_model
+            m = self.eval_lens if isinstance(self.eval_lens, LensModel) else LensModel.from_json(self.eval_lens)
+            if m.size is not None and m.size != S:
+                m = m.scaled(S[1] / m.size[1], S[0] / m.size[0])
+            zt = E.lens_zones([image_model(m, h, w, S) for h, w in sizes])
+        return E.letterbox_scales(sizes, S), zt
 
     def eval(self, model, evaluator, is_distributed, half=False):
         """Eval-mode forward of every validation batch, ``evaluator.update`` on the decoded predictions, ``summarize``.
@@ -241,8 +284,13 @@ class Exp(BaseExp):
         try:
             with torch.no_grad():
                 for images, targets, _, _ in evaluator.dataloader:
+                    tables = ()
+                    if evaluator.strata is not None:      # object sizes in original pixels, zones in the input frame
+                        from ep24.jpeg import finish_checked
+                        images = finish_checked(images)
+                        tables = self.eval_tables([tuple(im.shape[:2]) for im in images])
                     imgs, labs = transform.batch(images, targets, tuple(self.test_size))
-                    evaluator.update(model(imgs, train=False) if views is None else tta.predict(model, imgs, views), labs)
+                    evaluator.update(model(imgs, train=False) if views is None else tta.predict(model, imgs, views), labs, *tables)
             stats = evaluator.summarize()
         finally:
             if views is not None:

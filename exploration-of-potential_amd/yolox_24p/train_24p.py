@@ -553,6 +553,38 @@ def apply_eval_args(exp, args):
             exp.eval_tta_scales = tuple(float(s) for s in args.eval_tta_scales)
     if getattr(args, "eval_vote", None) is not None:
         exp.eval_vote = float(args.eval_vote)
+    msg = check_eval_strata_args(args)
+    if msg:
+        raise SystemExit("train_24p.py: " + msg)
+    if getattr(args, "eval_areas", False):
+        exp.eval_areas = True
+    if getattr(args, "eval_zones", None) is not None:
+        exp.eval_zones = args.eval_zones
+        if getattr(args, "eval_zone_edges", None) is not None:
+            exp.eval_zone_edges = tuple(float(e) for e in args.eval_zone_edges)
+        if args.eval_zones == "lens":
+            exp.eval_lens = args.eval_lens
+
+
+def check_eval_strata_args(args):
+    """--eval-zones lens needs its calibration file and --eval-lens belongs to it; --eval-zone-edges belongs to --eval-zones, ascends
+    and leaves room for the area rows (8 strata in all).  Returns the message of what is wrong, or None."""
+    zones, edges, lens = getattr(args, "eval_zones", None), getattr(args, "eval_zone_edges", None), getattr(args, "eval_lens", None)
+    if zones == "lens" and not lens:
+        return "--eval-zones lens takes the incidence angles from a calibration: add --eval-lens LENS.json"
+    if lens and zones != "lens":
+        return "--eval-lens is the calibration of --eval-zones lens (add --eval-zones lens)"
+    if lens and not os.path.isfile(lens):
+        return "--eval-lens %s: no such calibration file (JSON: K, D, pinhole, fov_deg, size)" % lens
+    if edges is not None:
+        if zones is None:
+            return "--eval-zone-edges names the zones of --eval-zones (add --eval-zones radius or lens)"
+        e = [float(x) for x in edges]
+        if len(e) < 2 or any(not a < b for a, b in zip(e, e[1:])):
+            return "--eval-zone-edges %s: at least two edges, ascending (the last may be inf)" % (" ".join(str(x) for x in edges),)
+        if len(e) - 1 + (4 if getattr(args, "eval_areas", False) else 1) > 8:
+            return "--eval-zone-edges: %d zones and the area rows make more than 8 strata" % (len(e) - 1)
+    return None
 
 
 class _Parser(argparse.ArgumentParser):
@@ -650,7 +682,20 @@ def make_parser():
     p.add_argument("--eval-vote", default=None, type=float, metavar="T", help="polygon voting in the evaluation: every kept detection "
                    "becomes the score-weighted consensus of the candidates whose area IoU with it is above T (needs --nms-iou poly24 "
                    "or --eval-tta)")
+    add_eval_strata_flags(p)
     return p
+
+
+def add_eval_strata_flags(p):
+    """The flags of the stratified evaluation (ep24.evaluate strata), shared with eval_24p.py."""
+    p.add_argument("--eval-areas", action="store_true", help="evaluate by object size too: pycocotools' twelve lines (AP / AR for all, "
+                   "small, medium, large objects in original-image pixels; maxDets 1, 10, 100)")
+    p.add_argument("--eval-zones", default=None, choices=["radius", "lens"], help="AP per distortion zone of the objects' centres: "
+                   "radius = distance from the image centre in units of half the diagonal, lens = incidence angle by --eval-lens")
+    p.add_argument("--eval-zone-edges", default=None, type=float, nargs="+", metavar="E", help="with --eval-zones: the zones' edges, "
+                   "ascending, the last may be inf (default 0 1/3 2/3 inf for radius, 0 30 60 90 degrees for lens)")
+    p.add_argument("--eval-lens", default=None, type=str, metavar="LENS.json", help="with --eval-zones lens: the calibration of the "
+                   "validation images (the JSON of --fisheye-lens), scaled to every image from its size")
 
 
 def main(exp, args):

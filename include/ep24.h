@@ -977,6 +977,51 @@ int ep24_mask_boundary(const uint32_t* bits, const int64_t* tab, int N, int H, i
 int ep24_segm_iou_min(double* iou, const double* other, int64_t n, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * E8  24-point evaluation by strata of object size and distortion zone (csrc/evalstrata.hip; DESIGN.md section 7;
+ *     ep24.evaluate.Evaluator24(strata=...)).  E1's matcher with pycocotools' area-range semantics, the range widened to a stratum
+ *     {area_lo, area_hi, z_lo, z_hi} (double): an object with area A and zone value z lies outside it iff A < area_lo || A > area_hi ||
+ *     z < z_lo || z >= z_hi (area closed at both ends as pycocotools' ranges, zone half open so that zones partition).  At most 8 strata.
+ *     Measures, both double, every operation rounded on its own:
+ *       area = (0.5 * |sum over k = 0..23 of (x_k * y_{k+1} - x_{k+1} * y_k)|) / (s * s), the sum from 0.0 in that order over the
+ *         object's 24 points converted from fp32 (a GT's: label columns 3..50; a detection's: c + r_k * (cos, sin)(15 deg * k), product
+ *         and sum in fp32 as E1 forms them), s = scales[image] = input pixels per original pixel: areas in original-image pixels.
+ *       zone from the centre (X, Y) (a GT's: label columns 1, 2; a detection's: row columns 0, 1) and the image's row of zt[B][16] =
+ *         {kind, fx, fy, cx, cy, k1, k2, k3, k4, theta_max, thetad(theta_max), 0...}: x = (X - cx) / fx, y = (Y - cy) / fy,
+ *         rd = sqrt(x * x + y * y) (a plain sqrt, not hypot).  kind 0: z = 0.  kind 1: z = rd.  kind 2: z = theta * (180 / pi) with theta
+ *         the result of ep24_lens_points' 12 clamped Newton steps on td = fmin(rd, thetad(theta_max)), and z = +infinity where
+ *         rd > thetad(theta_max).  Any other kind reads as 0.
+ *     Nothing allocates, frees or synchronises; the only atomics are integer ones (npig, the append offset); every result is a bit-exact
+ *     function of the inputs.
+ * ep24_eval_measure: out[n][2] double = (area, zone) of rows[n][ncols] fp32, row_kind 0 = label rows (ncols >= 51), 1 = detection rows
+ *   (ncols >= 26); image[n] int32 names every row's entry of scales[B] and zt[B][16]; an index outside [0, B) reads nothing and gives
+ *   (NaN, NaN).  n == 0 is EP24_OK.  EP24_E_ARG: a row_kind other than 0 / 1, ncols too small, a null pointer with n > 0.
+ * ep24_eval_match_strata: ep24_eval_match's arguments, meaning and limits, plus scales[B], zt[B][16] (device) and strata[NA][4] - a HOST
+ *   array, read during the call.  Per image, class, stratum a and threshold t, evaluateImg without crowd: a GT is ignored iff it lies
+ *   outside stratum a; the class's first max_dets detections go in (score desc, r asc) order; among the GTs not yet matched at (a, t)
+ *   with iou >= min(thr, 1 - 1e-10) the match is the lexicographic maximum of (not ignored, iou, row) - the best non-ignored GT if one
+ *   qualifies, else the best ignored one, equal IoUs to the later row.  A matched detection gets its TP bit and inherits the GT's ignore
+ *   flag; an unmatched one is ignored iff it lies outside the stratum itself.  rec_m[n][NA] int32 = 10 TP bits | 10 ignore bits << 16
+ *   (the layout ep24_segm_accumulate reads); rec_key, rec_cls, rec_p as ep24_eval_match; rec_val[n][2] double (nullable) = the
+ *   detection's (area, zone).  npig[num_classes][NA] += the non-ignored GTs.  EP24_E_UNSUPPORTED: NA outside 1..8 and ep24_eval_match's
+ *   limits; EP24_E_ARG: strata null or a stratum with lo > hi (or a NaN), and ep24_eval_match's.  B == 0 launches nothing.
+ * ep24_eval_accumulate_strata: ep24_segm_accumulate's kernel and tables - precision[10][101][K][NA][NM], recall[10][K][NA][NM] - with
+ *   NA <= 8 and NM <= 4 (EP24_E_UNSUPPORTED beyond); a record's position is the low 7 bits of its key.
+ * ------------------------------------------------------------------------------------------------ */
+int ep24_eval_measure(const float* rows, int ncols, int row_kind, const int32_t* image, int n, const double* scales,
+                      const double* zt, int B, const float* ray_cs, double* out, void* stream);
+int ep24_eval_match_strata(const float* labels, int L, int B, const float* rows, int ncols, const int64_t* row_off,
+                           const int32_t* keep, int64_t keep_stride, const int32_t* count, const float* conf,
+                           const int32_t* cls, int num_classes, int iou_type, const float* ray_cs, const double* iou_thr,
+                           int max_dets, int64_t seq_base, int64_t* sort_scratch, int P, const double* scales,
+                           const double* zt, const double* strata, int NA, int64_t* rec_key, int32_t* rec_cls,
+                           int32_t* rec_p, int32_t* rec_m, double* rec_val, int32_t* rec_count, int32_t* npig,
+                           int32_t* err, void* stream);
+int ep24_eval_accumulate_strata(const int32_t* order, const int64_t* rec_key, const int32_t* rec_cls, const int32_t* rec_m,
+                                int64_t n, const int32_t* npig, int num_classes, int NA, const int32_t* max_dets, int NM,
+                                const double* rec_thr, int32_t* ctp_scratch, double* env_scratch, double* precision,
+                                double* recall, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * N1 input pipeline (yolox_24p/datasets/data_augment.py:109-174)
  * ------------------------------------------------------------------------------------------------ */
 /* preproc for n images (n <= 65535): images = raw uint8 HWC sources in one device buffer; desc[n][6] int64 =
