@@ -9,7 +9,8 @@ save every image with its 24-point detections drawn on it.
 ``ep24.draw.draw_detections`` on the ORIGINAL image with the letterbox ratio - the reference's ``Evaluator.eval`` /
 ``save_eval_results`` / ``vis`` (:266-367) without the host-side OpenCV.  Results go to ``<output_dir>/<timestamp>/``: the drawn
 image under its own name, ``<name>.dets.npy`` with the ``[n, 29]`` float32 rows beside it, and one ``detections.json`` (file, size,
-ratio, count).  ``--save-segm FILE`` also writes every detection of the run as a COCO "segm" result (``ep24.results``: the polygon
+ratio, count).  ``--track`` reads the folder's files in sorted order as the frames of one sequence (``ep24.track.Tracker24``: one frame at a time
+whatever ``-b`` is; the drawn label and colour are the track's id; ``--save-tracks FILE`` writes MOTChallenge ``.txt`` or ``.json``).  ``--save-segm FILE`` also writes every detection of the run as a COCO "segm" result (``ep24.results``: the polygon
 rasterised on the original image and run-length encoded on the GPU).  ``.npy`` (uint8 HWC) and binary PPM are read and written natively; JPEG / PNG / BMP through PIL when it is installed.  Without it
 baseline JPEG files are read AND written through ``ep24.jpeg`` (``--jpeg-encoder``, ``--jpeg-quality``; the drawn device tensors of a
 batch are encoded in one call), and a ``.png`` / ``.bmp`` name ends in a clear message.
@@ -190,6 +191,13 @@ class Evaluator:
             from ep24.labels24 import COCO_IDS
             from ep24.results import SegmResults
             segm = SegmResults(COCO_IDS if args.segm_category_ids == "coco" else None)
+        tracker, track_frames, frame_no = None, [], 0
+        if getattr(args, "track", False):
+            from ep24 import track
+            # one stream; postprocess's rows are in score order, so a frame with more than the cap keeps its best rows
+            tracker = track.Tracker24(streams=1, max_tracks=256, max_dets=track.MAX_DETS, high_thre=args.track_high, low_thre=args.track_low,
+                                      new_thre=args.track_new, match_thre=args.track_match, max_age=args.track_max_age,
+                                      min_hits=args.track_min_hits, device=self.device)
         step = max(int(args.batch_size), 1)
         for lo in range(0, len(self.file_list), step):
             names = self.file_list[lo:lo + step]
@@ -205,8 +213,17 @@ class Evaluator:
                                       nms_iou=args.nms_iou, vote_thre=getattr(args, "vote", None))
             drawn_batch = []
             for name, img, ratio, dets in zip(names, originals, ratios, outputs):
-                drawn = draw_detections(img, dets, ratio=ratio, conf=args.draw_conf, num_classes=self.num_classes,
-                                        class_names=self.class_names, fill_alpha=args.fill_alpha, show_scores=args.show_scores)
+                if tracker is not None:
+                    frame_no += 1
+                    tracks = tracker.update([None if dets is None else dets[:tracker.N]])[0]
+                    drawn = track.draw_tracks(img, tracks, ratio=ratio, conf=args.draw_conf, fill_alpha=args.fill_alpha,
+                                              show_scores=args.show_scores)
+                    np.save(os.path.join(self.save_folder, name + ".ids.npy"), tracks.ids.cpu().numpy())
+                    track_frames.append((frame_no, track.Tracks(tracks.dets.cpu(), tracks.ids.cpu(), tracks.hits.cpu()), float(ratio)))
+                    dets = tracks.dets if tracks.dets.shape[0] else None          # the rows saved and exported are the tracks'
+                else:
+                    drawn = draw_detections(img, dets, ratio=ratio, conf=args.draw_conf, num_classes=self.num_classes,
+                                            class_names=self.class_names, fill_alpha=args.fill_alpha, show_scores=args.show_scores)
                 rows = np.zeros((0, 29), dtype=np.float32) if dets is None else dets.float().cpu().numpy()
                 drawn_batch.append(drawn)
                 np.save(os.path.join(self.save_folder, name + ".dets.npy"), rows)
@@ -219,8 +236,14 @@ class Evaluator:
             write_images([os.path.join(self.save_folder, f) for f in names], drawn_batch, args.jpeg_encoder, args.jpeg_quality,
                          getattr(args, "jpeg_entropy", "host"))
         with open(os.path.join(self.save_folder, "detections.json"), "w") as fh:
-            json.dump({"input_size": list(self.input_size), "conf": args.conf, "nms": args.nms, "nms_iou": args.nms_iou,
-                       "tta": bool(getattr(args, "tta", False)), "vote": getattr(args, "vote", None), "draw_conf": args.draw_conf, "images": records}, fh, indent=1)
+            summary = {"input_size": list(self.input_size), "conf": args.conf, "nms": args.nms, "nms_iou": args.nms_iou,
+                       "tta": bool(getattr(args, "tta", False)), "vote": getattr(args, "vote", None), "draw_conf": args.draw_conf, "images": records}
+            if tracker is not None:                             # the rows of every image are then its shown tracks, ids in <name>.ids.npy
+                summary["track"] = True
+            json.dump(summary, fh, indent=1)
+        if tracker is not None and args.save_tracks:
+            n = track.write_tracks(args.save_tracks, track_frames)
+            print("saved %d track rows of %d frames to %s" % (n, frame_no, args.save_tracks))
         if segm is not None:
             segm.dump(args.save_segm)
             print("saved %d segm results to %s" % (len(segm), args.save_segm))
@@ -253,10 +276,30 @@ def check_tta_args(args):
     return None
 
 
+def check_track_args(args):
+    """--save-tracks and the --track-* thresholds belong to --track; the tracker's own argument rules (ep24.track.check_args) are
+    applied here, before a model is built.  Returns the message of the refusal, or None."""
+    if not getattr(args, "track", False):
+        if getattr(args, "save_tracks", None):
+            return "--save-tracks writes the tracks of --track: add --track"
+        return None
+    if args.track_new is None:
+        args.track_new = args.track_high + 0.1                  # ByteTrack: new = track + 0.1
+    if args.save_tracks and os.path.splitext(args.save_tracks)[1].lower() not in (".txt", ".json"):
+        return "--save-tracks %s: the name must end in .txt (MOTChallenge) or .json" % args.save_tracks
+    from ep24.track import check_args
+    try:
+        check_args(high_thre=args.track_high, low_thre=args.track_low, new_thre=args.track_new, match_thre=args.track_match,
+                   max_age=args.track_max_age, min_hits=args.track_min_hits)
+    except ValueError as e:
+        return "--track: %s" % e
+    return None
+
+
 class _Parser(argparse.ArgumentParser):
     def parse_args(self, args=None, namespace=None):
         a = super().parse_args(args, namespace)
-        msg = check_tta_args(a)
+        msg = check_tta_args(a) or check_track_args(a)
         if msg:
             self.error(msg)
         return a
@@ -281,6 +324,18 @@ def make_parser():
                    "(implies --nms-iou poly24); one forward per view")
     p.add_argument("--vote", default=None, type=float, metavar="T", help="polygon voting: every kept detection becomes the score-weighted "
                    "consensus of the candidates whose area IoU with it is above T (needs --nms-iou poly24 or --tta)")
+    p.add_argument("--track", action="store_true", help="the files in sorted order are the frames of one sequence: detections are "
+                   "associated across them by the polygons' area IoU (ep24.track), one frame at a time whatever -b is, and drawn with "
+                   "their track id as label and colour")
+    p.add_argument("--track-high", default=0.5, type=float, help="--track: rows with score >= this are associated first (ByteTrack 0.5)")
+    p.add_argument("--track-low", default=0.1, type=float, help="--track: rows below this score are ignored (ByteTrack 0.1)")
+    p.add_argument("--track-new", default=None, type=float, help="--track: an unmatched row starts a track from this score "
+                   "(default: --track-high + 0.1)")
+    p.add_argument("--track-match", default=0.2, type=float, help="--track: first association needs area IoU above this (ByteTrack 1 - 0.8)")
+    p.add_argument("--track-max-age", default=30, type=int, help="--track: frames a lost track is kept (ByteTrack 30)")
+    p.add_argument("--track-min-hits", default=3, type=int, help="--track: matches before a track is confirmed and shown")
+    p.add_argument("--save-tracks", default=None, type=str, metavar="FILE", help="--track: write every shown track of every frame, "
+                   "MOTChallenge rows to a .txt name, the same plus the 26 shape numbers to a .json name")
     p.add_argument("--draw-conf", default=1e-4, type=float, help="detections below this score are not drawn (the reference's 0.0001)")
     p.add_argument("--fill-alpha", default=0, type=int, help="0..255: blend the class colour over the polygon's inside (0 = outline only)")
     p.add_argument("--show-scores", action="store_true", help="append the score's two decimals to the label")

@@ -693,6 +693,62 @@ int ep24_post_vote_poly24(const float* pred, int ncols, const float* score, int 
                           const int32_t* keep_count, float* voted, int32_t* n_voters, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * T1  tracking: identity of 24-point detections across frames (csrc/track.hip; ep24.track; DESIGN.md section 7, "Tracking").
+ *     S streams, T track slots per stream, N detection rows per stream.  A frame is ep24_track_cost, then ep24_track_step: two
+ *     launches whose grids follow from S, T and N alone, no host synchronisation, no floating-point atomics.
+ *   State, owned by the caller; a tracker starts from all-zero tables with hdr[s][0] = 1:
+ *     trk_f [S][T][32] fp32: 0..25 shape (cx, cy, r_0..r_23), 26, 27 velocity (vx, vy), 28 score, 29..31 zero.
+ *     trk_i [S][T][8] int32: 0 id (0 = free slot: all of its words in both tables are zero), 1 class, 2 status (1 tentative,
+ *       2 confirmed, 3 lost), 3 hits, 4 age (frames since the last match), 5 frame of birth (the frame counter after that step:
+ *       the first frame is 1), 6 detection row of the last match or -1, 7 zero.
+ *     hdr [S][4] int32: next id (ids are never reused), frame counter, spawns dropped so far because the table was full, live slots.
+ *   Input: det [S][N][ncols] fp32, ncols >= 29, postprocess's rows (cx, cy, 24 radii, obj_conf, class_conf, class); count [S]:
+ *     rows at and beyond count[s] are ignored and not read.  score = the single fp32 product det[26] * det[27]; class = (int)det[28].
+ *     A row is eligible iff d < count[s] and score >= low_thre (a NaN score is not).
+ * ep24_track_cost writes every word of iou [S][T][N] double and dscore [S][N] fp32 (the score of an eligible row, NaN otherwise).
+ *     The predicted polygon of a live slot: centre p = (cx + vx, cy + vy), one fp32 add each, radii unchanged, vertices
+ *     p + r_k * ray_cs (cos in ray_cs[k], sin in ray_cs[24 + k]; product and sum separate fp32 operations, as ep24_post_nms_poly24
+ *     forms them); a row's polygon likewise from its own 26 values.  iou[s][t][d] = poly24_iou(a = predicted polygon of slot t,
+ *     b = polygon of row d) of csrc/poly24.h when the slot is live, the row eligible and the classes agree (or class_agnostic);
+ *     0.0 otherwise.  Pairs whose fp32 vertex boxes do not overlap with positive width and height have IoU exactly 0.0 and are not
+ *     evaluated; a pair with a NaN vertex on either side is evaluated, and its NaN is stored as it is (it never matches).
+ *     EP24_E_ARG: a null pointer, S, T or N < 1, ncols < 29, low_thre not finite.  EP24_E_UNSUPPORTED: T not a multiple of 64 or
+ *     above 1024, N above 4096, S above 65535.
+ * ep24_track_step, one workgroup per stream, on the iou and dscore the cost call left (same det, S, T, N):
+ *   Stage 1: the live slots against the eligible rows with score >= high_thre; a pair is admissible iff iou > (double)match_thre.
+ *   Stage 2: the slots stage 1 left unmatched that were confirmed with age 0 before the step, against the eligible rows with
+ *     score < high_thre; admissible iff iou > (double)match_low_thre.
+ *   Either stage matches greedily by the strict total order (iou descending, slot ascending, row ascending): take the first
+ *     admissible pair, remove its slot and its row, repeat.  (Computed as rounds of mutual best - every unmatched slot takes its
+ *     best admissible unmatched row, ties to the lower row; every row its best slot, ties to the lower slot; mutual choices are
+ *     matched - which gives the same set; the number of rounds depends on the data, nothing else of the launch does.)  A NaN iou
+ *     is never admissible.
+ *   Matched slot, row z, with p the predicted centre and e = z_c - p: c = p + alpha * e; v = v + beta * e;
+ *     r_k = r_k + gamma * (z_k - r_k); every operation a separate fp32 one.  score = the row's; the class stays; hits += 1;
+ *     age = 0; word 6 = the row; a tentative slot becomes confirmed when hits >= min_hits, a lost slot becomes confirmed.
+ *   Unmatched live slot: a tentative one is freed; any other gets age += 1 and is freed when age > max_age, else its status
+ *     becomes lost, c = p (it coasts), v stays, word 6 = -1.
+ *   Spawns: the rows of stage 1 left unmatched with score >= new_thre, in ascending row order; the k-th of them takes the k-th
+ *     free slot in ascending slot order, the slots freed in this step included: the row's 26 shape values bit for bit, v = 0,
+ *     score, class, hits = 1, age = 0, id = next id + k, status tentative when min_hits > 1, else confirmed, birth = this frame,
+ *     word 6 = the row.  A row without a free slot adds 1 to the dropped counter and takes no id.
+ *   hdr: next id += spawns placed; frame counter += 1; dropped; live slots after the step.
+ *   Outputs, every word written: det_track [S][N] int32 = the id matched to or spawned from row d, else 0.  out_f [S][T][29],
+ *     out_i [S][T][4]: one row per slot that is confirmed with age 0 after the step, in ascending slot order - out_f = the 26
+ *     filtered values, then columns 26..28 of the matched (or spawning) row; out_i = id, row, hits, slot; the rows after them are
+ *     zero.  out_count [S] = their number.
+ *   EP24_E_ARG: a null pointer, S, T or N < 1, ncols < 29, a threshold that is not finite, match_thre or match_low_thre < 0 (the
+ *     box pre-test is exact from 0), a gain outside [0, 1], min_hits < 1, max_age < 0.  EP24_E_UNSUPPORTED: T not a multiple of 64
+ *     or above 1024, N above 4096.
+ * ------------------------------------------------------------------------------------------------ */
+int ep24_track_cost(const float* det, int ncols, const int32_t* count, const float* trk_f, const int32_t* trk_i, int S, int T,
+                    int N, float low_thre, int class_agnostic, const float* ray_cs, double* iou, float* dscore, void* stream);
+int ep24_track_step(const float* det, int ncols, const double* iou, const float* dscore, float* trk_f, int32_t* trk_i,
+                    int32_t* hdr, int S, int T, int N, float high_thre, float new_thre, float match_thre, float match_low_thre,
+                    float alpha, float beta, float gamma, int max_age, int min_hits, int32_t* det_track, float* out_f,
+                    int32_t* out_i, int32_t* out_count, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * E1  evaluation: COCO-style AP of 24-point detections (pycocotools evaluateImg + accumulate, area "all", no crowd /
  *     ignore, one maxDets; csrc/evaluate.hip).  iou_type 0 = circle24 (mean over the 24 rays of the ray circles' IoU,
  *     fp32), 1 = rect (axis-aligned boxes, float64), 2 = poly24 (exact area IoU of the two 24-gons, float64: GT vertices
