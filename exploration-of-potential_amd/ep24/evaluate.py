@@ -280,13 +280,14 @@ class Evaluator24:
         self.num_classes = int(num_classes)
         self.iou_type = iou_type
         self._t = _iou_type(iou_type)
+        self._mds = mds
         self.max_dets = mds[-1] if self.strata is None else mds       # an int without strata, as ever
         self.conf_thre, self.nms_thre = float(conf_thre), float(nms_thre)
         self.device = device
         self.reset()
 
     def reset(self):
-        self._recs = []                                   # per batch: (key, cls, p, tp) device tensors; with strata (.., m, val)
+        self._recs = []                                   # per batch: (key, cls, p, m [n, NA], val [n, 2] or None) device tensors
         self._npig = None
         self._err = None
         self.seq = 0                                      # images seen: the next image's sequence number
@@ -404,58 +405,54 @@ class Evaluator24:
             ms = _match_scratch[key] = _MatchScratch(B, P, cap, dev, NA)
         ms.count.zero_()
         cs, thr, _ = _device_consts(dev)
+        head = [ptr(lab), lab.shape[1], B, ptr(rows), ncols, ptr(row_off), ptr(keep), keep_stride, ptr(count), ptr(conf), ptr(cls),
+                self.num_classes, self._t, ptr(cs), ptr(thr), self._mds[-1], self.seq, ptr(ms.sort), P]
+        recs = [ptr(ms.key), ptr(ms.cls), ptr(ms.p), ptr(ms.tp)]
+        tail = [ptr(ms.count), ptr(self._npig), ptr(self._err), stream_ptr()]
         if NA:
             sc, zt = _h2d(tables[0], dev), _h2d(tables[1], dev)
-            call("eval_match_strata", ptr(lab), lab.shape[1], B, ptr(rows), ncols, ptr(row_off), ptr(keep), keep_stride, ptr(count),
-                 ptr(conf), ptr(cls), self.num_classes, self._t, ptr(cs), ptr(thr), self.max_dets[-1], self.seq, ptr(ms.sort), P,
-                 ptr(sc), ptr(zt), self._strata_rows.ctypes.data, NA, ptr(ms.key), ptr(ms.cls), ptr(ms.p), ptr(ms.tp), ptr(ms.val),
-                 ptr(ms.count), ptr(self._npig), ptr(self._err), stream_ptr())
+            call("eval_match_strata", *head, ptr(sc), ptr(zt), self._strata_rows.ctypes.data, NA, *recs, ptr(ms.val), *tail)
         else:
-            call("eval_match", ptr(lab), lab.shape[1], B, ptr(rows), ncols, ptr(row_off), ptr(keep), keep_stride, ptr(count), ptr(conf),
-                 ptr(cls), self.num_classes, self._t, ptr(cs), ptr(thr), self.max_dets, self.seq, ptr(ms.sort), P, ptr(ms.key),
-                 ptr(ms.cls), ptr(ms.p), ptr(ms.tp), ptr(ms.count), ptr(self._npig), ptr(self._err), stream_ptr())
+            call("eval_match", *head, *recs, *tail)
         n = int(ms.count.item())                          # the batch's one host synchronisation
-        if n and NA:
-            self._recs.append((ms.key[:n].clone(), ms.cls[:n].clone(), ms.p[:n].clone(), ms.tp[:n * NA].view(n, NA).clone(),
-                               ms.val[:2 * n].view(n, 2).clone()))
-        elif n:
-            self._recs.append((ms.key[:n].clone(), ms.cls[:n].clone(), ms.p[:n].clone(), ms.tp[:n].clone()))
+        if n:
+            w = max(NA, 1)
+            self._recs.append((ms.key[:n].clone(), ms.cls[:n].clone(), ms.p[:n].clone(), ms.tp[:n * w].view(n, w).clone(),
+                               ms.val[:2 * n].view(n, 2).clone() if NA else None))
         self.n_records += n
         self.seq += B
 
     # ---- accumulation ------------------------------------------------------------------------------
     def _sorted(self):
-        """The records of the evaluation sorted by (class, score desc, image seq, rank): (key, cls, p, tp, order) on the device."""
+        """The records of the evaluation sorted by (class, score desc, image seq, rank): (key, cls, p, m, order) on the device,
+        m [n, NA] (one column without strata: the TP bits)."""
         dev = self.device
         if self._recs:
-            key = torch.cat([r[0] for r in self._recs])
-            cls = torch.cat([r[1] for r in self._recs])
-            p = torch.cat([r[2] for r in self._recs])
-            tp = torch.cat([r[3] for r in self._recs])
+            key, cls, p, m = (torch.cat([r[i] for r in self._recs]) for i in range(4))
         else:
             key = torch.zeros(0, dtype=torch.int64, device=dev)
-            cls = p = tp = torch.zeros(0, dtype=torch.int32, device=dev)
-        if self.strata and tp.dim() == 1:
-            tp = tp.view(0, len(self.strata))
+            cls = p = torch.zeros(0, dtype=torch.int32, device=dev)
+            m = torch.zeros(0, len(self.strata) if self.strata else 1, dtype=torch.int32, device=dev)
         order = sort_records(key, cls, 7 + max(self.seq - 1, 0).bit_length(), max(self.num_classes - 1, 0).bit_length())
-        return key, cls, p, tp, order
+        return key, cls, p, m, order
 
     def records(self):
         """Host copy of the sorted records: dict of numpy arrays cls, score (fp32), seq, rank, p, tp (10-bit masks); with strata
         also m [n, NA] (10 TP bits | 10 ignore bits << 16; tp is the first stratum's TP bits), area and zone of the detections."""
         if self._npig is None:
             raise Ep24Error("ep24: no update() yet")
-        key, cls, p, tp, order = self._sorted()
+        key, cls, p, m, order = self._sorted()
         o = order.long()
         k = key[o].cpu().numpy().view(np.uint64)
         sbits = (~(k >> np.uint64(32))).astype(np.uint32)
         sbits = np.where(sbits & np.uint32(0x80000000), sbits & np.uint32(0x7FFFFFFF), ~sbits).astype(np.uint32)
+        m = m[o].cpu().numpy()
         rec = {"cls": cls[o].cpu().numpy(), "score": sbits.view(np.float32), "seq": ((k >> np.uint64(7)) & np.uint64((1 << 25) - 1)).astype(np.int64),
-               "rank": (k & np.uint64(127)).astype(np.int64), "p": p[o].cpu().numpy(), "tp": tp[o].cpu().numpy()}
+               "rank": (k & np.uint64(127)).astype(np.int64), "p": p[o].cpu().numpy(), "tp": m[:, 0] & 0x3FF}
         if self.strata:
             val = torch.cat([r[4] for r in self._recs]) if self._recs else torch.zeros(0, 2, dtype=torch.float64, device=self.device)
             val = val[o].cpu().numpy()
-            rec.update(m=rec["tp"], tp=rec["tp"][:, 0] & 0x3FF, area=val[:, 0], zone=val[:, 1])
+            rec.update(m=m, area=val[:, 0], zone=val[:, 1])
         return rec
 
     def npig(self):
@@ -465,44 +462,33 @@ class Evaluator24:
         n = self._npig.cpu().numpy().astype(np.int64)
         return n.reshape(self.num_classes, len(self.strata)) if self.strata else n
 
-    def _accumulate_strata(self):
-        dev, C, NA, NM = self.device, self.num_classes, len(self.strata), len(self.max_dets)
-        key, cls, p, m, order = self._sorted()
-        n = key.numel()
-        _, _, rthr = _device_consts(dev)
-        npr, nrc = 10 * 101 * C * NA * NM, 10 * C * NA * NM
-        out = torch.empty(npr + nrc, dtype=torch.float64, device=dev)
-        ctp = torch.empty(NA * NM * max(n, 1), dtype=torch.int32, device=dev)
-        env = torch.empty(NA * NM * max(n, 1), dtype=torch.float64, device=dev)
-        md = _h2d(np.array(self.max_dets, dtype=np.int32), dev)
-        call("eval_accumulate_strata", ptr(order), ptr(key), ptr(cls), ptr(m.contiguous()), n, ptr(self._npig), C, NA, ptr(md), NM,
-             ptr(rthr), ptr(ctp), ptr(env), ptr(out), ptr(out, npr), stream_ptr())
-        if int(self._err.item()):
-            raise Ep24Error("ep24: eval_match_strata met an image with more detections than its scratch holds")
-        host = out.cpu().numpy()
-        return host[:npr].reshape(10, 101, C, NA, NM), host[npr:].reshape(10, C, NA, NM)
-
     def accumulate(self):
         """-> (precision [10, 101, C], recall [10, C]) float64 numpy arrays: one device-to-host copy.  With strata:
         (precision [10, 101, C, NA, NM], recall [10, C, NA, NM])."""
         if self._npig is None:
             raise Ep24Error("ep24: no update() yet")
         _lib.require_gpu()
-        if self.strata:
-            return self._accumulate_strata()
         dev, C = self.device, self.num_classes
-        key, cls, p, tp, order = self._sorted()
+        shape = (C, len(self.strata), len(self._mds)) if self.strata else (C,)
+        key, cls, p, m, order = self._sorted()
         n = key.numel()
         _, _, rthr = _device_consts(dev)
-        out = torch.empty(10 * 101 * C + 10 * C, dtype=torch.float64, device=dev)
-        ctp = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
-        env = torch.empty(max(n, 1), dtype=torch.float64, device=dev)
-        call("eval_accumulate", ptr(order), ptr(cls), ptr(tp), n, ptr(self._npig), C, ptr(rthr), None, ptr(ctp), ptr(env),
-             ptr(out), ptr(out, 10 * 101 * C), stream_ptr())
+        cols = int(np.prod(shape[1:]))                    # NA * NM tables per class
+        npr, nrc = 10 * 101 * C * cols, 10 * C * cols
+        out = torch.empty(npr + nrc, dtype=torch.float64, device=dev)
+        ctp = torch.empty(cols * max(n, 1), dtype=torch.int32, device=dev)
+        env = torch.empty(ctp.numel(), dtype=torch.float64, device=dev)
+        if self.strata:
+            md = _h2d(np.array(self._mds, dtype=np.int32), dev)
+            call("eval_accumulate_strata", ptr(order), ptr(key), ptr(cls), ptr(m), n, ptr(self._npig), C, shape[1], ptr(md), shape[2],
+                 ptr(rthr), ptr(ctp), ptr(env), ptr(out), ptr(out, npr), stream_ptr())
+        else:
+            call("eval_accumulate", ptr(order), ptr(cls), ptr(m), n, ptr(self._npig), C, ptr(rthr), None, ptr(ctp), ptr(env), ptr(out),
+                 ptr(out, npr), stream_ptr())
         if int(self._err.item()):
-            raise Ep24Error("ep24: eval_match met an image with more detections than its scratch holds")
+            raise Ep24Error("ep24: eval_match%s met an image with more detections than its scratch holds" % ("_strata" if self.strata else ""))
         host = out.cpu().numpy()
-        return host[:10 * 101 * C].reshape(10, 101, C), host[10 * 101 * C:].reshape(10, C)
+        return host[:npr].reshape(10, 101, *shape), host[npr:].reshape(10, *shape)
 
     def summarize(self):
         precision, recall = self.accumulate()

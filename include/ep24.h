@@ -750,7 +750,7 @@ int ep24_track_step(const float* det, int ncols, const double* iou, const float*
 
 /* ------------------------------------------------------------------------------------------------
  * E1  evaluation: COCO-style AP of 24-point detections (pycocotools evaluateImg + accumulate, area "all", no crowd /
- *     ignore, one maxDets; csrc/evaluate.hip).  iou_type 0 = circle24 (mean over the 24 rays of the ray circles' IoU,
+ *     ignore, one maxDets; csrc/evaluate.hip, the match kernel in csrc/evalgeom.h).  iou_type 0 = circle24 (mean over the 24 rays of the ray circles' IoU,
  *     fp32), 1 = rect (axis-aligned boxes, float64), 2 = poly24 (exact area IoU of the two 24-gons, float64: GT vertices
  *     against c + r_k * (cos, sin)(15 deg * k) formed in fp32; csrc/poly24.h).  ray_cs[48] = cos(15 deg * k), then
  *     sin(15 deg * k), fp32.
@@ -1033,7 +1033,7 @@ int ep24_mask_boundary(const uint32_t* bits, const int64_t* tab, int N, int H, i
 int ep24_segm_iou_min(double* iou, const double* other, int64_t n, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
- * E8  24-point evaluation by strata of object size and distortion zone (csrc/evalstrata.hip; DESIGN.md section 7;
+ * E8  24-point evaluation by strata of object size and distortion zone (csrc/evalstrata.hip, csrc/evalgeom.h; DESIGN.md section 7;
  *     ep24.evaluate.Evaluator24(strata=...)).  E1's matcher with pycocotools' area-range semantics, the range widened to a stratum
  *     {area_lo, area_hi, z_lo, z_hi} (double): an object with area A and zone value z lies outside it iff A < area_lo || A > area_hi ||
  *     z < z_lo || z >= z_hi (area closed at both ends as pycocotools' ranges, zone half open so that zones partition).  At most 8 strata.

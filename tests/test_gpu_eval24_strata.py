@@ -259,6 +259,96 @@ def test_bad_arguments_launch_nothing():
     assert bool((out == -7.0).all())
 
 
+# ---- the two instances of the one match kernel, at C level ---------------------------------------------
+def _match_sources():
+    """{name: (labels, rows, ncols, row_off, keep, keep_stride, count, conf, cls, C, P, cap)}: the scene as ``update_detections``
+    hands it over (29 columns, no keep / conf / cls) and a B = 2, 320^2 synthetic head as ``update`` does (rows through post_nms'
+    keep, class and confidence from post_prepare's arrays)."""
+    scene = SC.make_scene(5, 256)
+    counts = [0 if d is None else len(d) for d in scene["dets"]]
+    rows = dev(np.concatenate([d for d in scene["dets"] if d is not None]))
+    off = np.zeros(5, dtype=np.int64)
+    off[1:] = np.cumsum(counts)[:-1]
+    src = {"update_detections": (dev(scene["labels"]), rows, 29, dev(off), None, 0, dev(np.array(counts, dtype=np.int32)), None, None, 120,
+                                 E._pow2(max(counts)), sum(counts))}
+    B, S, C = 2, 320, 80
+    pred = synth.decode_head(synth.make_raw_head(B, S, seed=21, num_classes=C), S)
+    pred[..., 26:] = torch.sigmoid(pred[..., 26:])
+    pred = pred.to(DEV).float().contiguous()
+    labels = synth.make_labels(B, [6, 12], size=S, seed=22).to(DEV).float().contiguous()
+    E.Evaluator24(C, conf_thre=0.01).update(pred, labels)       # post_prepare + post_nms: their outputs stay in the scratch
+    A = pred.shape[1]
+    ws = infer._scratch[(B, A, str(pred.device))]
+    src["update"] = (labels, pred, 27 + C, E._row_offs[(B, A, str(pred.device))], ws.keep, A, ws.count, ws.conf, ws.cls, C, E._pow2(A), B * A)
+    return src
+
+
+def test_plain_and_one_stratum_instances_agree_at_c_level():
+    """ep24_eval_match and ep24_eval_match_strata (one all-inclusive stratum, scale 1, no zones) on the same buffers: the same
+    records, TP bits, GT counts, no ignore bit, for every IoU type and both detection sources."""
+    cs, thr, _ = E._device_consts(torch.device(DEV))
+    one = np.array([E.Stratum("all").row()], dtype=np.float64)
+    for name, (labels, rows, ncols, row_off, keep, stride, count, conf, cls, C, P, cap) in _match_sources().items():
+        B = labels.shape[0]
+        sc, zt = torch.ones(B, dtype=torch.float64, device=DEV), dev(E.no_zones(B))
+        for iou_type in ("circle24", "rect", "poly24"):
+            got = []
+            for strata in (False, True):
+                key = torch.zeros(cap, dtype=torch.int64, device=DEV)
+                rcls, rp, rm = (torch.zeros(cap, dtype=torch.int32, device=DEV) for _ in range(3))
+                cnt, npig, err = (torch.zeros(k, dtype=torch.int32, device=DEV) for k in (1, C, 1))
+                sort = torch.zeros(B * P, dtype=torch.int64, device=DEV)
+                head = [ptr(labels), labels.shape[1], B, ptr(rows), ncols, ptr(row_off), ptr(keep), stride, ptr(count), ptr(conf), ptr(cls), C,
+                        E.IOU_TYPES[iou_type], ptr(cs), ptr(thr), 100, 0, ptr(sort), P]
+                recs, tail = [ptr(key), ptr(rcls), ptr(rp), ptr(rm)], [ptr(cnt), ptr(npig), ptr(err), stream_ptr()]
+                if strata:
+                    call("eval_match_strata", *head, ptr(sc), ptr(zt), one.ctypes.data, 1, *recs, None, *tail)
+                else:
+                    call("eval_match", *head, *recs, *tail)
+                n = int(cnt.item())
+                k, c, p, m = (t[:n].cpu().numpy() for t in (key, rcls, rp, rm))
+                o = np.lexsort((k, c))
+                got.append((n, k[o], c[o], p[o], m[o], npig.cpu().numpy(), int(err.item())))
+            (n0, k0, c0, p0, tp, g0, e0), (n1, k1, c1, p1, m, g1, e1) = got
+            what = (name, iou_type)
+            assert n0 == n1 > 0 and e0 == 0 and e1 == 0, what
+            assert np.array_equal(k0, k1) and np.array_equal(c0, c1) and np.array_equal(p0, p1), what
+            assert np.array_equal(tp, m & 0x3FF) and not (m >> 16).any(), what
+            assert tp.any() or name == "update", what                                 # the random head need not hit a GT
+            assert np.array_equal(g0, g1) and g0.sum() > 0, what
+
+
+def test_plain_match_bad_arguments_launch_nothing():
+    """The counterpart of the eval_match_strata cases above for ep24_eval_match: every output and scratch buffer pre-filled and
+    unchanged, the message names the argument as name=value."""
+    scene = SC.make_scene(2, 8)
+    labels = dev(scene["labels"])
+    dets = [dev(x) for x in scene["dets"]]
+    rows = torch.cat(dets)
+    n = rows.shape[0]
+    cs, thr, _ = E._device_consts(rows.device)
+    row_off = dev(np.array([0, dets[0].shape[0]], dtype=np.int64))
+    count = dev(np.array([d.shape[0] for d in dets], dtype=np.int32))
+    conf = torch.ones(n, dtype=torch.float32, device=DEV)
+
+    def match(name, L=8, max_dets=100, P=256, conf=None, iou_type=0):
+        out = [torch.full((n,), -7, dtype=dt, device=DEV) for dt in (torch.int64, torch.int32, torch.int32, torch.int32)]
+        cnt, npig, err = (torch.full((k,), -7, dtype=torch.int32, device=DEV) for k in (1, 120, 1))
+        sort = torch.full((2 * 256,), -7, dtype=torch.int64, device=DEV)
+        with pytest.raises(Ep24Error, match=name):
+            call("eval_match", ptr(labels), L, 2, ptr(rows), 29, ptr(row_off), None, 0, ptr(count), ptr(conf), None, 120, iou_type, ptr(cs),
+                 ptr(thr), max_dets, 0, ptr(sort), P, ptr(out[0]), ptr(out[1]), ptr(out[2]), ptr(out[3]), ptr(cnt), ptr(npig), ptr(err),
+                 stream_ptr())
+        torch.cuda.synchronize()
+        assert all(bool((t == -7).all()) for t in out + [cnt, npig, err, sort]), name
+
+    match("L=257", L=257)
+    match("max_dets=129", max_dets=129)
+    match("P=192", P=192)
+    match("cls=null", conf=conf)
+    match("iou_type=3", iou_type=3)
+
+
 # ---- entry points --------------------------------------------------------------------------------------
 def _small_exp():
     sys.path.insert(0, Y24)

@@ -1,9 +1,9 @@
-"""Launch the stratified match kernel (csrc/evalstrata.hip) beside the single-range one on one fixed batch, for
+"""Launch the match kernel's instance with strata (csrc/evalgeom.h) beside the single-range one on one fixed batch, for
 
     rocprofv3 --kernel-trace --stats -- python tools/eval_strata_timing.py
 
 B = 20 images, 50 GTs each, 8 400 anchors at conf 0.01 (synthetic eval-mode predictions through post_prepare + post_nms, as
-``Evaluator24.update`` runs them).  ``eval_match_kernel``, ``eval_match_strata_kernel`` at NA = 1 and at NA = 8 (the four COCO area
+``Evaluator24.update`` runs them).  ``eval_match_kernel<GW, false>``, ``eval_match_kernel<GW, true>`` at NA = 1 and at NA = 8 (the four COCO area
 rows and four lens zones) are launched ``--reps`` times each on the same buffers; the trace tells the three apart by their order.
 Prints one JSON line with GPU-event times per launch, for a run without the profiler.
 """
